@@ -21,8 +21,15 @@ transmission, velocity, rne, actuation, qfrc_smooth) and the dense kernel
 mjw::dense_kernel<7, ...> (Cholesky + M^-1, CG solve, Euler).  As in the
 reference's benchmark (benchmark.py:123-155) the step is captured once as a
 hipGraph (after the first warmup step) and replayed every step, the control noise
-launched before each replay; the timed region holds graph replays only.  The whole
-Data state is saved right before it; after it the state is restored and the same
+launched before each replay; the timed region holds graph replays only.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps,
+write `--dump-outputs DIR` (the Data arrays the last timed step left, float32 .npy,
+at most 64 MB; the inputs are the same from run to run) and print the result line
+with `roofline` and `cpu_baseline` null.  Everything below runs with `--full` only.
+
+With `--full` the whole
+Data state is saved right before the timed region; after it the state is restored and the same
 steps (same state, same control-noise indices, so bitwise the same work) run again
 eagerly through mjw_step_trace, which records a HIP event on that stream after every
 kernel launch and so times each kernel over exactly the timed window.  The record
@@ -150,14 +157,14 @@ def parse():
   p.add_argument("--solver", default=None, choices=["CG", "NEWTON"], help="override opt.solver (default: the config's)")
   p.add_argument("--nconmax", type=int, default=None)
   p.add_argument("--njmax", type=int, default=None)
-  p.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle on rank 0 (0 = skip)")
+  p.add_argument("--cpu-baseline", type=int, default=1, help="with --full: time the CPU oracle on rank 0 (0 = skip)")
   p.add_argument("--cpu-worlds", type=int, default=None, help="CPU baseline sample worlds (default: the config's, 1024)")
   p.add_argument("--cpu-steps", type=int, default=None, help="CPU baseline sample steps (default: the config's, 1000)")
   p.add_argument("--pmc", default=None, help="PMC traffic summary (default: the newest profiles/pmc_<model>_rNN.json)")
   p.add_argument("--graph", type=int, default=1, help="capture mjw.step once as a hipGraph and replay it every step "
                  "(benchmark.py:123-155: ctrl noise is launched outside the graph); 0 = launch the step eagerly")
   p.add_argument("--trace-steps", type=int, default=0,
-                 help="after the timed region the Data state saved before it is restored and the first --trace-steps "
+                 help="with --full: after the timed region the Data state saved before it is restored and the first --trace-steps "
                  "of the same timed steps (0 = all of them) run again eagerly with a HIP event after each kernel "
                  "launch (mjw_step_trace): the per-kernel durations of `roofline`; every timed step is a graph replay")
   p.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -166,6 +173,14 @@ def parse():
                  help="independent world shards per rank, each with its own Data and HIP stream (measured slower "
                  "than one batch on the humanoid: 12.2 vs 13.9 M env-steps/s)")
   p.add_argument("--dump-qpos", default=None, help="directory: each rank writes its final qpos + world offset (tests)")
+  p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                 help="after the timed steps write the Data arrays the last timed step left (DUMP_FIELDS) as DIR/<name>.npy, "
+                 "float32, at most 64 MB in all (a fixed seeded sample of worlds when larger); ranks > 0 write "
+                 "DIR/<name>_rank<r>.npy")
+  p.add_argument("--full", action="store_true",
+                 help="also run what the headline figure does not need: the eager per-kernel trace pass over the timed "
+                 "window with `roofline` and the trace checks, and `cpu_baseline` (see --cpu-baseline, --trace-steps, --pmc); "
+                 "without it the run sets up, warms up, times the steps and prints the result line")
   a = p.parse_args()
   if a.gpus is None:  # torchrun without --gpus: one rank per process of the launch
     a.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -370,6 +385,39 @@ def restore(d, saved):
     v.copy_(saved[k])
 
 
+# --dump-outputs: the per-world Data arrays a caller of mjw.step reads after it (state, kinematics, forces,
+# sensors, solver statistics); the contact / constraint pools are left out (workspace, sized by nconmax / njmax)
+DUMP_FIELDS = ("time", "qpos", "qvel", "act", "ctrl", "qacc", "qacc_warmstart", "xpos", "xquat", "xipos", "geom_xpos",
+               "site_xpos", "subtree_com", "cvel", "actuator_force", "qfrc_bias", "qfrc_passive", "qfrc_actuator",
+               "qfrc_smooth", "qacc_smooth", "qfrc_constraint", "sensordata", "flexvert_xpos", "nefc", "solver_niter")
+DUMP_BYTES = 64 * 2**20
+
+
+def dump_outputs(path, shards, rank, nranks):
+  """Write DUMP_FIELDS of the rank's worlds (the shards concatenated) as float32 .npy files.  When they exceed
+  the rank's share of DUMP_BYTES, every array keeps the same sorted sample of worlds, drawn with a fixed seed
+  from the world count alone, so two runs with the same arguments write the same worlds."""
+  import torch
+
+  os.makedirs(path, exist_ok=True)
+  arrays = {}
+  for name in DUMP_FIELDS:
+    t = torch.cat([getattr(dk, name) for dk in shards])
+    if t.numel():
+      arrays[name] = t
+  nworld = sum(dk.nworld for dk in shards)
+  per_world = sum(4 * t.numel() // nworld for t in arrays.values())
+  keep = min(nworld, max(1, (DUMP_BYTES // nranks) // per_world))
+  ids = None
+  if keep < nworld:
+    ids = torch.as_tensor(np.sort(np.random.default_rng(0).choice(nworld, keep, replace=False)), device=shards[0].qpos.device)
+  suffix = f"_rank{rank}" if rank else ""
+  for name, t in arrays.items():
+    if ids is not None:
+      t = t[ids]
+    np.save(os.path.join(path, f"{name}{suffix}.npy"), t.float().cpu().numpy())
+
+
 def _free_port():
   import socket
 
@@ -501,7 +549,8 @@ def main():
 
   # the timed region: K graph replays (or K eager steps when capture failed), nothing else
   nefc_t0, ncon_t0 = sizes()
-  saved = [snapshot(dk) for dk in shards]  # the state the timed window starts from (restored for the trace)
+  # --full: the state the timed window starts from (restored for the trace)
+  saved = [snapshot(dk) for dk in shards] if args.full else None
   torch.cuda.synchronize()
   if world > 1:
     dist.barrier()
@@ -516,25 +565,29 @@ def main():
   nefc_t1, ncon_t1 = sizes()
   qpos_all = torch.cat([dk.qpos for dk in shards])
   qpos_timed = qpos_all.clone()
-  # per-kernel durations over the timed window itself: restore the saved state and run the first `ntrace`
-  # timed steps again eagerly with one HIP event after every kernel launch (mjw_step_trace); every world is
-  # computed by one wave from its own data, so these are the timed steps' kernels, with the same nefc /
-  # ncon, which the algorithmic bytes of `roofline` are priced at (mean over the traced steps)
-  ntrace = args.steps if args.trace_steps <= 0 else min(args.trace_steps, args.steps)
-  for dk, sv in zip(shards, saved):
-    restore(dk, sv)
-  del saved
-  acc = torch.zeros(2, dtype=torch.float64, device=dev)
-  for i in range(ntrace):
-    one_step(args.warmup + i, traced=True)
-    acc[0] += shards[0].nefc.sum()
-    acc[1] += shards[0].nacon[0]
-  torch.cuda.synchronize()
-  tab = kernel_table(tracer.durations(), bool(m.is_sparse))
-  nefc_mean, ncon_mean = (float(x) / (ntrace * shards[0].nworld) for x in acc.cpu())
-  trace_sum = sum(e["ms_per_step"] for e in tab.values())
-  # a full re-run of the window ends in the timed run's state, bitwise (the replay of the same work)
-  replay_bitwise = bool(torch.equal(shards[0].qpos, qpos_timed[: shards[0].nworld])) if ntrace == args.steps else None
+  if args.dump_outputs:  # what the last timed step left, before the trace pass rewinds the state
+    dump_outputs(args.dump_outputs, shards, rank, world)
+  tab, ntrace = {}, 0
+  if args.full:
+    # per-kernel durations over the timed window itself: restore the saved state and run the first `ntrace`
+    # timed steps again eagerly with one HIP event after every kernel launch (mjw_step_trace); every world is
+    # computed by one wave from its own data, so these are the timed steps' kernels, with the same nefc /
+    # ncon, which the algorithmic bytes of `roofline` are priced at (mean over the traced steps)
+    ntrace = args.steps if args.trace_steps <= 0 else min(args.trace_steps, args.steps)
+    for dk, sv in zip(shards, saved):
+      restore(dk, sv)
+    del saved
+    acc = torch.zeros(2, dtype=torch.float64, device=dev)
+    for i in range(ntrace):
+      one_step(args.warmup + i, traced=True)
+      acc[0] += shards[0].nefc.sum()
+      acc[1] += shards[0].nacon[0]
+    torch.cuda.synchronize()
+    tab = kernel_table(tracer.durations(), bool(m.is_sparse))
+    nefc_mean, ncon_mean = (float(x) / (ntrace * shards[0].nworld) for x in acc.cpu())
+    trace_sum = sum(e["ms_per_step"] for e in tab.values())
+    # a full re-run of the window ends in the timed run's state, bitwise (the replay of the same work)
+    replay_bitwise = bool(torch.equal(shards[0].qpos, qpos_timed[: shards[0].nworld])) if ntrace == args.steps else None
   converged = int((~torch.isnan(qpos_all).any(dim=1)).sum())
   solver_niter_mean = float(torch.cat([dk.solver_niter for dk in shards]).float().mean())
   solver_niter_max = int(torch.cat([dk.solver_niter for dk in shards]).max())
@@ -557,19 +610,32 @@ def main():
 
   value = total_worlds * args.steps / elapsed
   if rank == 0:
-    words = step_words(mjm, m.nv_pad, bool(m.is_sparse))
-    # a sparse efc row carries njrow values + njrow column indices instead of an nv_pad dense row
-    groups_alg = b_alg_groups(mjm, words, nefc_mean, ncon_mean, 2 * m.njrow if m.is_sparse else m.nv_pad, bool(m.is_sparse))
-    # worlds per timed launch: shard 0's
-    nlaunch = d.nworld
-    pmc, pmc_src = None, "no PMC summary"
-    for path in args.pmc:
-      pmc, pmc_src = pmc_traffic(path, args.model, nlaunch, solver_name)
-      if pmc is not None:
-        break
-    row_w = 2 * m.njrow if m.is_sparse else m.nv_pad
-    roof = roofline_record(tab, groups_alg, nlaunch, pmc, pmc_src,
-                           lambda ne, nc: b_alg_groups(mjm, words, ne, nc, row_w, bool(m.is_sparse)))
+    roof, trace_cfg = None, {}
+    if args.full:
+      words = step_words(mjm, m.nv_pad, bool(m.is_sparse))
+      # a sparse efc row carries njrow values + njrow column indices instead of an nv_pad dense row
+      groups_alg = b_alg_groups(mjm, words, nefc_mean, ncon_mean, 2 * m.njrow if m.is_sparse else m.nv_pad, bool(m.is_sparse))
+      # worlds per timed launch: shard 0's
+      nlaunch = d.nworld
+      pmc, pmc_src = None, "no PMC summary"
+      for path in args.pmc:
+        pmc, pmc_src = pmc_traffic(path, args.model, nlaunch, solver_name)
+        if pmc is not None:
+          break
+      row_w = 2 * m.njrow if m.is_sparse else m.nv_pad
+      roof = roofline_record(tab, groups_alg, nlaunch, pmc, pmc_src,
+                             lambda ne, nc: b_alg_groups(mjm, words, ne, nc, row_w, bool(m.is_sparse)))
+      trace_cfg = {
+        "trace_steps": ntrace,
+        "trace_window": "the timed steps themselves: state restored to the timed region's start, steps "
+                        f"{args.warmup}..{args.warmup + ntrace - 1} re-run eagerly with HIP events per launch",
+        "trace_kernel_sum_ms_per_step": trace_sum,
+        "trace_over_timed": trace_sum / (elapsed / args.steps * 1e3),
+        "trace_consistent": trace_sum <= 1.03 * (elapsed / args.steps * 1e3),
+        "trace_replay_bitwise": replay_bitwise,
+        "nefc_mean": nefc_mean,
+        "ncon_mean": ncon_mean,  # both: mean over the traced (= timed) steps
+      }
     if args.scaling == "weak":
       parallelism = f"{args.nworld} worlds per rank on {world} GPU(s) (weak), no collective"
     else:
@@ -601,17 +667,10 @@ def main():
         "graph": graphs is not None,
         **({"graph_error": graph_error} if graph_error else {}),
         "timed_region": "graph replays only" if graphs is not None else "eager steps (no graph)",
-        "trace_steps": ntrace,
-        "trace_window": "the timed steps themselves: state restored to the timed region's start, steps "
-                        f"{args.warmup}..{args.warmup + ntrace - 1} re-run eagerly with HIP events per launch",
-        "trace_kernel_sum_ms_per_step": trace_sum,
-        "trace_over_timed": trace_sum / (elapsed / args.steps * 1e3),
-        "trace_consistent": trace_sum <= 1.03 * (elapsed / args.steps * 1e3),
-        "trace_replay_bitwise": replay_bitwise,
+        "full": bool(args.full),
+        **trace_cfg,  # --full: the trace pass's record (trace_*, nefc_mean / ncon_mean over the traced steps)
         "converged_worlds": converged,
-        "nefc_mean": nefc_mean,
-        "ncon_mean": ncon_mean,
-        "nefc_ncon_window": "mean over the traced (= timed) steps; timed region start / end: "
+        "nefc_ncon_window": "timed region start / end: "
                             f"nefc {nefc_t0:.2f} / {nefc_t1:.2f}, ncon {ncon_t0:.2f} / {ncon_t1:.2f}",
         "solver_niter_mean": solver_niter_mean,
         "solver_niter_max": solver_niter_max,
@@ -620,7 +679,7 @@ def main():
       "roofline": roof,
       "cpu_baseline": None,
     }
-    if world == 1 and args.cpu_baseline:
+    if args.full and world == 1 and args.cpu_baseline:
       out["cpu_baseline"] = cpu_baseline(mjm, args.cpu_worlds, args.cpu_steps, cfg["key"], args.njmax, args.nconmax, args.model)
     print(json.dumps(out), flush=True)
   if world > 1:

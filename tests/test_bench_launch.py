@@ -70,7 +70,7 @@ def test_gpu_bench_two_ranks_weak_equals_single(tmp_path, model, per_rank):
 
 @pytest.mark.gpu
 def test_gpu_bench_two_ranks_strong_and_graph(tmp_path):
-  common = ["--steps", "5", "--warmup", "2", "--cpu-baseline", "0", "--nworld", "301", "--trace-steps", "2"]
+  common = ["--full", "--steps", "5", "--warmup", "2", "--cpu-baseline", "0", "--nworld", "301", "--trace-steps", "2"]
   strong = _run(["--gpus", "2", "--scaling", "strong", "--graph", "0", "--dump-qpos", str(tmp_path / "s")] + common)
   assert strong["scaling"] == "strong" and strong["config"]["nworld_total"] == 301
   # graph replay over two stream shards of one rank: the timed region is replays only, the kernel times
@@ -82,6 +82,70 @@ def test_gpu_bench_two_ranks_strong_and_graph(tmp_path):
   got = [np.load(tmp_path / "s" / f"qpos_rank{r}.npz") for r in range(2)]
   assert [int(z["offset"]) for z in got] == [0, 151]
   np.testing.assert_array_equal(np.concatenate([z["qpos"] for z in got]), qg)
+
+
+@pytest.mark.gpu
+def test_gpu_bench_plain_run_and_dump_outputs(tmp_path):
+  """A plain run times its steps and reports the headline only (no trace pass, roofline or CPU baseline);
+  --dump-outputs writes the last timed step's Data arrays as float32, the same from run to run."""
+  args = ["--gpus", "1", "--nworld", "70", "--steps", "3", "--warmup", "2"]
+  runs = [_run(args + ["--dump-outputs", str(tmp_path / tag)]) for tag in ("a", "b")]
+  rec = runs[0]
+  assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["dtype"] == "fp32" and rec["higher_is_better"] is True
+  assert abs(rec["value"] - 70 * 1e3 / rec["ms_per_step"]) <= 1e-6 * rec["value"]
+  assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["config"]["full"] is False
+  assert "trace_steps" not in rec["config"] and rec["config"]["converged_worlds"] == 70
+  names = sorted(os.listdir(tmp_path / "a"))
+  assert names == sorted(os.listdir(tmp_path / "b")) and {"qpos.npy", "qvel.npy", "qacc.npy", "xpos.npy", "nefc.npy"} <= set(names)
+  total = 0
+  for n in names:
+    a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+    assert a.dtype == np.float32 and a.shape[0] == 70 and np.isfinite(a).all(), n
+    np.testing.assert_array_equal(a, b, err_msg=n)
+    total += a.nbytes
+  assert 0 < total <= 64 * 2**20
+  q = np.load(tmp_path / "a" / "qpos.npy")
+  assert q.shape == (70, 28) and np.abs(q[0] - q[1]).max() > 0  # the ctrl noise differs per world: the steps ran
+
+
+def test_dump_outputs_samples_a_fixed_set_of_worlds(tmp_path, monkeypatch):
+  """Above the byte budget every array keeps the same seeded sample of worlds, in world order."""
+  import types
+
+  import torch
+
+  sys.path.insert(0, ROOT)
+  import bench
+
+  def shard(lo, n):
+    ids = torch.arange(lo, lo + n, dtype=torch.float32)
+    d = types.SimpleNamespace(nworld=n)
+    for name in bench.DUMP_FIELDS:
+      setattr(d, name, torch.zeros(n, 0))
+    d.qpos = ids[:, None] * torch.ones(1, 5)
+    d.xpos = ids[:, None, None] * torch.ones(1, 2, 3)
+    d.nefc = ids.to(torch.int32)
+    return d
+
+  shards = [shard(0, 60), shard(60, 40)]
+  per_world = 4 * (5 + 6 + 1)
+  monkeypatch.setattr(bench, "DUMP_BYTES", 25 * per_world + 7)
+  for tag in ("a", "b"):
+    bench.dump_outputs(str(tmp_path / tag), shards, 0, 1)
+  assert sorted(os.listdir(tmp_path / "a")) == ["nefc.npy", "qpos.npy", "xpos.npy"]  # empty fields are not written
+  got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("qpos", "xpos", "nefc")}
+  assert all(v.dtype == np.float32 for v in got.values())
+  assert got["qpos"].shape == (25, 5) and got["xpos"].shape == (25, 2, 3) and got["nefc"].shape == (25,)
+  assert sum(v.nbytes for v in got.values()) <= 25 * per_world + 7
+  ids = got["nefc"]
+  assert (np.diff(ids) > 0).all() and ids.max() >= 60  # sorted, distinct, drawn over both shards
+  assert (got["qpos"] == ids[:, None]).all() and (got["xpos"] == ids[:, None, None]).all()
+  for n in got:
+    np.testing.assert_array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))
+  # within the budget every world is kept; other ranks write under their own names
+  monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 100 * per_world)
+  bench.dump_outputs(str(tmp_path / "c"), shards, 1, 2)
+  assert np.load(tmp_path / "c" / "qpos_rank1.npy").shape == (100, 5)
 
 
 def test_pmc_traffic_is_bound_to_the_kernel_sources(tmp_path):

@@ -2,7 +2,7 @@
 
 usage: python tools/kernel_window.py <stats_dir> <warmup> <steps> [out.json]
 
-`bench.py --steps K --warmup W` runs W warm-up steps, K timed steps (graph replays) and then -- from the
+`bench.py --full --steps K --warmup W` runs W warm-up steps, K timed steps (graph replays) and then -- from the
 state saved before the timed region -- the same K steps again eagerly for its HIP-event trace.  The step
 kernel `mjw::reset_counters_kernel` is launched once per step, so the kernel-trace CSV (ordered by start
 time) splits into steps at its dispatches: steps [W, W+K) are the timed window, [W+K, W+2K) its traced

@@ -28,7 +28,7 @@ print(a.nworld, s)") || exit 1
 # count 5 steps after 20 (their steps take ~20 ms).
 steps_stats=20; warm_stats=5; steps_pmc=20; warm_pmc=5
 case $M in aloha_cloth|cloth) steps_stats=20; warm_stats=20; steps_pmc=5; warm_pmc=20;; esac
-common="--model $M $sarg --cpu-baseline 0"
+common="--full --model $M $sarg --cpu-baseline 0"
 d=gpurun_out/prof_$tag
 rm -rf $d && mkdir -p $d
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $d/stats -o run -- python3 bench.py $common --steps $steps_stats --trace-steps $steps_stats --warmup $warm_stats > $d/stats.log 2>&1 || exit $?
