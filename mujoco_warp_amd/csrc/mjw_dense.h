@@ -7,8 +7,8 @@
 //   * keeps the mass matrix M and its inverse in the 32x32 MFMA accumulator layout
 //     (16 VGPRs each: lane l holds column l&31, rows 8*(r>>2) + 4*(l>>5) + (r&3)),
 //   * factors M = L L^T with rows in lanes and v_readlane broadcasts (no barriers),
-//     forms X = L^-1 with columns in lanes, and M^-1 = X^T X with 16
-//     v_mfma_f32_32x32x2_f32 (exact fp32 FMA chains),
+//     forms X = L^-1 in the MFMA operand layout (rows split over the two wave halves, L read
+//     back from LDS), and M^-1 = X^T X with 16 v_mfma_f32_32x32x2_f32 (exact fp32 FMA chains),
 //   * stages the constraint Jacobian once in LDS (odd row stride: conflict-free row
 //     and column reads) and keeps one constraint row per lane in VGPRs,
 //   * reduces over the wave with DPP (quad_perm / row_ror / row_bcast) + one readlane
@@ -67,17 +67,25 @@ __device__ __forceinline__ float symv(const f32x16& A, const float* vec, int h) 
   return xhalf_add(p0 + p1);
 }
 
-// SPD inverse.  a[k] = row (lane&31) of an SPD 32x32 matrix (identity-padded past n).
-// On return a[] holds row (lane&31) of L (A = L L^T, upper part zero); the result is
-// A^-1 in accumulator layout.  All broadcasts are v_readlane into SGPRs, so the only
-// live VGPR arrays are a[32], x[32] and the accumulator.
-// NB (>= n, compile time): the factor and substitution loops stop there -- rows and columns past n
-// are the identity, which the skipped steps would leave unchanged (exact), so a model with nv <= 16
-// does a quarter of the readlane / FMA work of the full 32 (the unrolled schedule is kept: no
-// runtime early-outs, which measured slower)
+// SPD inverse.  a[k] = row (lane&31) of an SPD 32x32 matrix (identity-padded past n); S: the 32x32 LDS
+// scratch (free on entry).  On return S holds the rows of L (A = L L^T, upper part zero; a[] is dead after
+// that store, which is what frees its registers) and the result is A^-1 in accumulator layout.
+// The Cholesky broadcasts are v_readlane into SGPRs.  X = L^-1 is formed directly in the layout the
+// X^T X MFMA reads -- lane (c, h) holds y[u] = X[2u + h][c] -- so the two wave halves work on different
+// rows of column c instead of repeating each other, and the multipliers L[2u + h][k] are f32x4 reads of
+// the stored L rows (one address per half: LDS broadcasts), not scalar broadcasts.  The one cross-half
+// value per step, X[k][c], is a v_permlane32_swap.  Every element of X gets the same multiply and the same
+// FMAs in the same k order as the columns-in-lanes form (spd_inverse_ref in mjw_dense.hip, kept for the
+// self-test): the result is bitwise the same.
+// NB (>= n, compile time, a multiple of 4): the factor and substitution loops stop there -- rows and
+// columns past n are the identity, which the skipped steps would leave unchanged (exact), so a model with
+// nv <= 16 does a quarter of the work of the full 32 (the unrolled schedule is kept: no runtime
+// early-outs, which measured slower).
+// STORE_L is kept for the callers' sake; the L rows are stored either way.
 template <bool STORE_L = false, int NB = 32>
-__device__ __forceinline__ f32x16 spd_inverse(float (&a)[32], int lane, float* S = nullptr) {
-  const int c = lane & 31;
+__device__ __forceinline__ f32x16 spd_inverse(float (&a)[32], int lane, float* S) {
+  static_assert(NB % 4 == 0 && NB <= 32, "the substitution works on blocks of four columns");
+  const int c = lane & 31, h = lane >> 5;
   // right-looking Cholesky, rows in lanes (wp.tile_cholesky, smooth.py:2860-2928);
   // 1/L[j][j] by v_rsq_f32 keeps the per-column critical path short
 #pragma unroll
@@ -88,31 +96,54 @@ __device__ __forceinline__ f32x16 spd_inverse(float (&a)[32], int lane, float* S
 #pragma unroll
     for (int k = j + 1; k < NB; k++) a[k] = fmaf(-a[j], rdlane(a[j], k), a[k]);
   }
-  if (STORE_L && lane < 32) {
+  __syncthreads();
+  if (lane < 32) {
     f32x4* rw = reinterpret_cast<f32x4*>(S + c * DSS);
 #pragma unroll
     for (int q = 0; q < 8; q++) rw[q] = f32x4{a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
   }
-  // X = L^-1, lane computes column c by right-looking forward substitution (critical path
-  // 32 steps, the other updates are independent); L[j][k] = readlane(a[k], j)
-  float x[32];
+  __syncthreads();
+  // X = L^-1 by right-looking forward substitution, four columns k = 4q .. 4q + 3 per block: the block's
+  // own four rows (y[2q], y[2q + 1]) are finished step by step, then every later row pair takes the four
+  // updates from one f32x4 of its L row (loading a block's rows just before their FMAs keeps the LDS reads
+  // from piling up in registers).  Lane k's pivot reciprocal is read from lane k.
+  const bool hi = h != 0;
+  const float rdiag = __builtin_amdgcn_rcpf(S[c * DSS + c]);
+  const float* Sh = S + h * DSS;
+  float y[16];
 #pragma unroll
-  for (int j = 0; j < 32; j++) x[j] = (c == j) ? 1.0f : 0.0f;
+  for (int u = 0; u < 16; u++) y[u] = (c == 2 * u + h) ? 1.0f : 0.0f;
 #pragma unroll
-  for (int k = 0; k < NB; k++) {
-    x[k] *= __builtin_amdgcn_rcpf(rdlane(a[k], k));
+  for (int q = 0; q < NB / 4; q++) {
+    const f32x4 La = *reinterpret_cast<const f32x4*>(Sh + (4 * q) * DSS + 4 * q);
+    const f32x4 Lb = *reinterpret_cast<const f32x4*>(Sh + (4 * q + 2) * DSS + 4 * q);
+    float xk[4];
 #pragma unroll
-    for (int j = k + 1; j < NB; j++) x[j] = fmaf(-rdlane(a[k], j), x[k], x[j]);
+    for (int kk = 0; kk < 4; kk++) {
+      const int k = 4 * q + kk, uk = k >> 1;
+      const bool hk = (k & 1) != 0;
+      const float sc = y[uk] * rdlane(rdiag, k);
+      y[uk] = (hi == hk) ? sc : y[uk];
+      // X[k][c] lives in half hk: r[0] = the lower half's value in both halves, r[1] = the upper half's
+      auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(y[uk]), __float_as_uint(y[uk]), false, false);
+      xk[kk] = __uint_as_float(hk ? r[1] : r[0]);
+      if (kk == 0) y[2 * q] = hi ? fmaf(-La[0], xk[0], y[2 * q]) : y[2 * q];  // row 4q + 1 only
+      if (kk < 2) y[2 * q + 1] = fmaf(-Lb[kk], xk[kk], y[2 * q + 1]);
+      if (kk == 2) y[2 * q + 1] = hi ? fmaf(-Lb[2], xk[2], y[2 * q + 1]) : y[2 * q + 1];  // row 4q + 3 only
+    }
+#pragma unroll
+    for (int u = 2 * q + 2; u < NB / 2; u++) {
+      const f32x4 Lr = *reinterpret_cast<const f32x4*>(Sh + (2 * u) * DSS + 4 * q);
+#pragma unroll
+      for (int kk = 0; kk < 4; kk++) y[u] = fmaf(-Lr[kk], xk[kk], y[u]);
+    }
   }
-  // A^-1 = X^T X : 16 x (32x32x2) f32 MFMA in two independent chains, operand X[2t + h][c]
-  const bool hi = lane >= 32;
+  // A^-1 = X^T X : 16 x (32x32x2) f32 MFMA in two independent chains, operand X[2t + h][c] = y[t]
   f32x16 r0 = {}, r1 = {};
 #pragma unroll
   for (int t = 0; t < 16; t += 2) {
-    float v0 = hi ? x[2 * t + 1] : x[2 * t];
-    float v1 = hi ? x[2 * t + 3] : x[2 * t + 2];
-    r0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, v0, r0, 0, 0, 0);
-    r1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, v1, r1, 0, 0, 0);
+    r0 = __builtin_amdgcn_mfma_f32_32x32x2f32(y[t], y[t], r0, 0, 0, 0);
+    r1 = __builtin_amdgcn_mfma_f32_32x32x2f32(y[t + 1], y[t + 1], r1, 0, 0, 0);
   }
   return r0 + r1;
 }

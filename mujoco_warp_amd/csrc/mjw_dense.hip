@@ -44,10 +44,47 @@ dense_kernel(const mjw_model_t m, const mjw_data_t d, int w0) {
   WLOG_END(wid, (FLAGS & DF_SOLVE) ? d.solver_niter[wid] : 0);
 }
 
+// The reference of spd_inverse's substitution, for the self-test only (no product kernel uses it): the
+// same Cholesky, then X = L^-1 with columns in lanes -- lanes c and c + 32 both compute column c by
+// right-looking forward substitution, L[j][k] = readlane(a[k], j) -- and the MFMA operand X[2t + h][c]
+// picked from x[] per half.  spd_inverse must reproduce it bit for bit.
+template <int NB>
+__device__ __forceinline__ f32x16 spd_inverse_ref(float (&a)[32], int lane) {
+  const int c = lane & 31;
+#pragma unroll
+  for (int j = 0; j < NB; j++) {
+    float piv = rdlane(a[j], j);
+    float inv = __builtin_amdgcn_rsqf(piv);
+    a[j] = (c > j) ? a[j] * inv : (c == j ? piv * inv : 0.0f);
+#pragma unroll
+    for (int k = j + 1; k < NB; k++) a[k] = fmaf(-a[j], rdlane(a[j], k), a[k]);
+  }
+  float x[32];
+#pragma unroll
+  for (int j = 0; j < 32; j++) x[j] = (c == j) ? 1.0f : 0.0f;
+#pragma unroll
+  for (int k = 0; k < NB; k++) {
+    x[k] *= __builtin_amdgcn_rcpf(rdlane(a[k], k));
+#pragma unroll
+    for (int j = k + 1; j < NB; j++) x[j] = fmaf(-rdlane(a[k], j), x[k], x[j]);
+  }
+  const bool hi = lane >= 32;
+  f32x16 r0 = {}, r1 = {};
+#pragma unroll
+  for (int t = 0; t < 16; t += 2) {
+    float v0 = hi ? x[2 * t + 1] : x[2 * t];
+    float v1 = hi ? x[2 * t + 3] : x[2 * t + 2];
+    r0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, v0, r0, 0, 0, 0);
+    r1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, v1, r1, 0, 0, 0);
+  }
+  return r0 + r1;
+}
+
 // device self-checks of the primitives above (mjw_selftest): which = 0 -> per-wave dsum and
-// xhalf_add of 64-lane chunks; which = 1 -> spd_inverse of 32x32 row-major SPD matrices; which = 2 ->
-// the same with the factor bound NB = 16 (matrices that are the identity past row / column 16);
-// which = 3 / 4 -> ldl_factor + ldl_solve (NB = 32 / 28) of one right-hand side per matrix
+// xhalf_add of 64-lane chunks; which = 1 -> spd_inverse of 32x32 row-major SPD matrices; which = 2 / 5 ->
+// the same with the factor bound NB = 16 / 28 (matrices that are the identity past row / column NB);
+// which = 3 / 4 -> ldl_factor + ldl_solve (NB = 32 / 28) of one right-hand side per matrix;
+// which = 6 / 7 / 8 -> spd_inverse_ref with NB = 32 / 16 / 28
 __global__ void __launch_bounds__(64) selftest_kernel(int which, const float* in, float* out, int n) {
   __shared__ __attribute__((aligned(16))) float S[DS_WORDS];
   const int w = blockIdx.x, lane = threadIdx.x;
@@ -78,8 +115,16 @@ __global__ void __launch_bounds__(64) selftest_kernel(int which, const float* in
     float a[32];
     f32x16 M;
     stage_spd(in + (long)w * 1024, 32, 32, nullptr, 0.0f, S, lane, a, M);
-    // which = 2: the NB = 16 bound (input identity past 16)
-    f32x16 Mi = which == 2 ? spd_inverse<false, 16>(a, lane) : spd_inverse(a, lane);
+    // stage_spd is done with S (it ends on a barrier)
+    f32x16 Mi;
+    switch (which) {
+      case 2: Mi = spd_inverse<false, 16>(a, lane, S); break;
+      case 5: Mi = spd_inverse<false, 28>(a, lane, S); break;
+      case 6: Mi = spd_inverse_ref<32>(a, lane); break;
+      case 7: Mi = spd_inverse_ref<16>(a, lane); break;
+      case 8: Mi = spd_inverse_ref<28>(a, lane); break;
+      default: Mi = spd_inverse<false, 32>(a, lane, S); break;
+    }
     const int c = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int r = 0; r < 16; r++) out[(long)w * 1024 + acc_row(r, h) * 32 + c] = Mi[r];
