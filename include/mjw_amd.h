@@ -18,6 +18,7 @@
  *                            com_vel / rne, passive.passive, constraint.make_constraint (one stage, below)
  *   mjw_sensor            <- sensor.sensor_pos/_vel/_acc  sensor.py:761,1377,2447
  *   mjw_ctrl_noise        <- benchmark.ctrl_noise         _src/benchmark.py:41-83
+ *   mjw_rays              <- ray.rays (no render context) ray.py:1212-1312
  *
  * Ownership: the caller owns every buffer (device pointers below); the library
  * never allocates or frees device memory and keeps no global mutable state.
@@ -33,7 +34,7 @@
 
 #include <stdint.h>
 
-#define MJW_ABI_VERSION 34
+#define MJW_ABI_VERSION 35
 
 /* ---- model: int scalars ---- */
 #define MJW_MODEL_INT_SCALARS(X)                                                                   \
@@ -220,6 +221,25 @@ typedef struct mjw_data_t {
   MJW_CONTACT_INT_ARRAYS(MJW_DECL_DIA)
 } mjw_data_t;
 
+/* Model fields that only ray casting reads (mjw_rays).  They are kept out of mjw_model_t, which is passed by
+ * value to every step kernel.  geom_rgba / mat_rgba are batchable like the model's float arrays: leading
+ * dim nb = 1 or nworld, world w reads row w % nb.  mesh_face holds vertex indices local to each mesh. */
+typedef struct mjw_ray_model_t {
+  int32_t ngeom;      /* must equal mjw_model_t.ngeom */
+  int32_t nmat;       /* materials */
+  int32_t nmeshface;  /* triangles of all meshes */
+  int32_t geom_rgba_nb;
+  int32_t mat_rgba_nb;
+  int32_t pad_;
+  const int32_t* geom_group;   /* (ngeom,) */
+  const int32_t* geom_matid;   /* (ngeom,) material id or -1 */
+  const float* geom_rgba;      /* (geom_rgba_nb, ngeom, 4) */
+  const float* mat_rgba;       /* (mat_rgba_nb, nmat, 4); may be NULL when nmat == 0 */
+  const int32_t* mesh_face;    /* (nmeshface, 3); may be NULL when nmeshface == 0 */
+  const int32_t* mesh_faceadr; /* (nmesh,) */
+  const int32_t* mesh_facenum; /* (nmesh,) */
+} mjw_ray_model_t;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -323,6 +343,19 @@ int mjw_sap_broadphase(const mjw_model_t* m, const mjw_data_t* d, int* collision
                        void* stream);
 int mjw_primitive_narrowphase(const mjw_model_t* m, const mjw_data_t* d, const int* collision_pair, const int* collision_pairid,
                               const int* collision_worldid, unsigned long long typemask, void* stream);
+
+/* Batched ray casting (ray.py:1212-1312 `rays` without a render context; ABI 35): for every world and ray the
+ * nearest geom along pnt + x vec, x >= 0, over all geom types at the frames d.geom_xpos / d.geom_xmat of
+ * the last position stage (no kinematics run here).  pnt / vec: device float (nb, nray, 3) with nb = 1 or
+ * d->nworld (world w reads row w % nb); vec is not normalised and dist is in units of |vec|.  geomgroup: six
+ * host ints or NULL (all -1 or NULL: no group filter, else geoms with geomgroup[clamp(geom_group, 0, 5)] == 0
+ * are skipped); flg_static == 0 skips geoms of bodies welded to the world; bodyexclude: device int (nray,),
+ * geoms of that body are skipped (-1: none).  Geoms with alpha 0 (their material's when they have one, else
+ * their own) are skipped.  Outputs, device: dist (nworld, nray), geomid (nworld, nray), normal (nworld, nray, 3);
+ * a miss gives -1, -1, 0; equal distances go to the lowest geom id.  nray == 0 is a successful no-op. */
+int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb, const float* vec,
+             int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude, float* dist, int* geomid,
+             float* normal, void* stream);
 
 #ifdef __cplusplus
 }

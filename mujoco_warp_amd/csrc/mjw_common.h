@@ -352,5 +352,7 @@ int sensor_launch(const mjw_model_t* m, const mjw_data_t* d, hipStream_t s, int 
 int sparse_launch(int stages, const mjw_model_t* m, const mjw_data_t* d, hipStream_t s);
 // per-world slot ranges of the contact pool (d->ncon_world) on the dense path, mjw_step.hip
 int pool_ranges_launch(const mjw_data_t* d, hipStream_t s);
+// sets the message mjw_last_error returns (for entry points outside mjw_step.hip) and returns `code`
+int set_last_error(int code, const char* msg);
 
 }  // namespace mjw

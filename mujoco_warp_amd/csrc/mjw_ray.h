@@ -1,0 +1,335 @@
+// mjw_ray.h -- ray / geom intersection routines (fp32, device), the per-lane part of mjw_rays.
+//
+// Semantics follow mujoco_warp/_src/ray.py (cited per routine).  Every routine takes the ray already mapped
+// into the geom's frame (ray_map: lp = mat' (pnt - pos), lv = mat' vec), returns the distance x >= 0 along
+// lv to the nearest hit (-1: no hit) and writes the surface normal in the geom's frame; the caller rotates
+// it to the world frame (rot_to_world).  lv is not normalised: x is in units of |lv|.  They keep no state and
+// read nothing but their arguments, so a sensor kernel can call them per lane as the ray kernel does.
+//
+// The touch sensor's distance-only routines (mjw_sensor.h ray_quad / ray_geom_local) are separate and
+// unchanged; these live in their own namespace.
+#pragma once
+
+#include "mjw_math.h"
+
+namespace mjw {
+namespace ray {
+
+enum : int { RG_PLANE = 0, RG_HFIELD = 1, RG_SPHERE = 2, RG_CAPSULE = 3, RG_ELLIPSOID = 4, RG_CYLINDER = 5, RG_BOX = 6, RG_MESH = 7 };
+
+// ray.py:33-49: the ray in the frame (pos, mat), mat row-major
+__device__ __forceinline__ void ray_map(const float* pos, const float* mat, const float* pnt, const float* vec, float* lp, float* lv) {
+  const float d[3] = {pnt[0] - pos[0], pnt[1] - pos[1], pnt[2] - pos[2]};
+  for (int i = 0; i < 3; i++) {
+    lp[i] = mat[i] * d[0] + mat[3 + i] * d[1] + mat[6 + i] * d[2];
+    lv[i] = mat[i] * vec[0] + mat[3 + i] * vec[1] + mat[6 + i] * vec[2];
+  }
+}
+
+__device__ __forceinline__ void rot_to_world(const float* mat, const float* nl, float* n) {
+  for (int i = 0; i < 3; i++) n[i] = mat[3 * i] * nl[0] + mat[3 * i + 1] * nl[1] + mat[3 * i + 2] * nl[2];
+}
+
+// ray.py:105-125: roots of a x^2 + 2 b x + c; returns the smaller non-negative one (-1: none), x0 <= x1 both
+__device__ __forceinline__ float quad_roots(float a, float b, float c, float& x0, float& x1) {
+  float det = b * b - a * c;
+  x0 = x1 = -1.0f;
+  if (det < MJW_MINVAL) return -1.0f;
+  det = sqrtf(det);
+  const float den = safe_div(1.0f, a);
+  x0 = (-b - det) * den;
+  x1 = (-b + det) * den;
+  return x0 >= 0.0f ? x0 : (x1 >= 0.0f ? x1 : -1.0f);
+}
+
+// conservative pre-test: can the ray p + x v, x >= 0, meet the ball |q - c|^2 <= r2?  (no MINVAL cut-off: a
+// grazing ray passes and the exact routine decides)
+__device__ __forceinline__ bool ball_test(const float* c, float r2, const float* p, const float* v) {
+  const float d[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
+  const float a = dot3(v, v), b = dot3(v, d), cc = dot3(d, d) - r2;
+  if (cc <= 0.0f) return true;           // origin inside
+  return b < 0.0f && b * b - a * cc >= 0.0f;  // heading towards it and the line meets it
+}
+
+// ray.py:187-208: front side only, inside the rendered rectangle when size[0] / size[1] > 0
+__device__ __forceinline__ float ray_plane(const float* size, const float* lp, const float* lv, float* nl) {
+  if (lv[2] > -MJW_MINVAL) return -1.0f;
+  const float x = -lp[2] / lv[2];
+  if (x < 0.0f) return -1.0f;
+  const float p0 = lp[0] + x * lv[0], p1 = lp[1] + x * lv[1];
+  if ((size[0] > 0.0f && fabsf(p0) > size[0]) || (size[1] > 0.0f && fabsf(p1) > size[1])) return -1.0f;
+  nl[0] = 0.0f; nl[1] = 0.0f; nl[2] = 1.0f;
+  return x;
+}
+
+// ray.py:211-225 (sphere of squared radius r2 at the frame origin)
+__device__ __forceinline__ float ray_sphere(float r2, const float* lp, const float* lv, float* nl) {
+  float x0, x1;
+  const float x = quad_roots(dot3(lv, lv), dot3(lv, lp), dot3(lp, lp) - r2, x0, x1);
+  if (x >= 0.0f) {
+    for (int i = 0; i < 3; i++) nl[i] = lp[i] + x * lv[i];
+    normalize3(nl);
+  }
+  return x;
+}
+
+// ray.py:228-299: the round side between the caps, then each cap's half sphere; normal radial or the cap's
+__device__ __forceinline__ float ray_capsule(const float* size, const float* lp, const float* lv, float* nl) {
+  const float r2 = size[0] * size[0], h = size[1];
+  float x = -1.0f, x0, x1;
+  float cap = 0.0f;  // z of the cap centre the hit belongs to (0: the round side)
+  bool side = true;
+  const float a2 = lv[0] * lv[0] + lv[1] * lv[1];
+  const float sol = quad_roots(a2, lv[0] * lp[0] + lv[1] * lp[1], lp[0] * lp[0] + lp[1] * lp[1] - r2, x0, x1);
+  if (sol >= 0.0f && fabsf(lp[2] + sol * lv[2]) <= h) x = sol;
+  const float a3 = a2 + lv[2] * lv[2];
+  for (int s = 1; s >= -1; s -= 2) {  // top cap, then bottom cap
+    const float cz = (float)s * h;
+    const float dz = lp[2] - cz;
+    quad_roots(a3, lv[0] * lp[0] + lv[1] * lp[1] + lv[2] * dz, lp[0] * lp[0] + lp[1] * lp[1] + dz * dz - r2, x0, x1);
+    const float xs[2] = {x0, x1};
+    for (int i = 0; i < 2; i++) {
+      const float z = lp[2] + xs[i] * lv[2];
+      if (xs[i] >= 0.0f && (s > 0 ? z >= h : z <= -h) && (x < 0.0f || xs[i] < x)) {
+        x = xs[i];
+        cap = cz;
+        side = false;
+      }
+    }
+  }
+  if (x >= 0.0f) {
+    nl[0] = lp[0] + x * lv[0];
+    nl[1] = lp[1] + x * lv[1];
+    nl[2] = side ? 0.0f : lp[2] + x * lv[2] - cap;
+    normalize3(nl);
+  }
+  return x;
+}
+
+// ray.py:302-330: normal = the gradient of the ellipsoid function at the hit
+__device__ __forceinline__ float ray_ellipsoid(const float* size, const float* lp, const float* lv, float* nl) {
+  float s[3], a = 0.0f, b = 0.0f, c = -1.0f, x0, x1;
+  for (int i = 0; i < 3; i++) {
+    s[i] = safe_div(1.0f, size[i] * size[i]);
+    a += s[i] * lv[i] * lv[i];
+    b += s[i] * lv[i] * lp[i];
+    c += s[i] * lp[i] * lp[i];
+  }
+  const float x = quad_roots(a, b, c, x0, x1);
+  if (x >= 0.0f) {
+    for (int i = 0; i < 3; i++) nl[i] = s[i] * (lp[i] + x * lv[i]);
+    normalize3(nl);
+  }
+  return x;
+}
+
+// ray.py:333-391: the flat ends inside the radius, the round side between them; normal +-z or radial
+__device__ __forceinline__ float ray_cylinder(const float* size, const float* lp, const float* lv, float* nl) {
+  const float r2 = size[0] * size[0], h = size[1];
+  float x = -1.0f, end = 0.0f, x0, x1;
+  if (fabsf(lv[2]) > MJW_MINVAL) {
+    for (int s = -1; s <= 1; s += 2) {
+      const float sol = ((float)s * h - lp[2]) / lv[2];
+      if (sol < 0.0f) continue;
+      const float p0 = lp[0] + sol * lv[0], p1 = lp[1] + sol * lv[1];
+      if (p0 * p0 + p1 * p1 <= r2 && (x < 0.0f || sol < x)) {
+        x = sol;
+        end = (float)s;
+      }
+    }
+  }
+  const float sol = quad_roots(lv[0] * lv[0] + lv[1] * lv[1], lv[0] * lp[0] + lv[1] * lp[1], lp[0] * lp[0] + lp[1] * lp[1] - r2, x0, x1);
+  if (sol >= 0.0f && fabsf(lp[2] + sol * lv[2]) <= h && (x < 0.0f || sol < x)) {
+    x = sol;
+    end = 0.0f;
+  }
+  if (x >= 0.0f) {
+    if (end == 0.0f) {
+      nl[0] = lp[0] + x * lv[0];
+      nl[1] = lp[1] + x * lv[1];
+      nl[2] = 0.0f;
+      normalize3(nl);
+    } else {
+      nl[0] = 0.0f; nl[1] = 0.0f; nl[2] = end;
+    }
+  }
+  return x;
+}
+
+// ray.py:397-448: the nearest face hit with x >= 0 (from inside: the far face); normal = the face's.
+// all (optional, 6 floats): the hit distance of each face, index 2 axis + (side + 1) / 2, -1 where missed.
+__device__ __forceinline__ float ray_box(const float* size, const float* lp, const float* lv, float* nl, float* all) {
+  float x = -1.0f;
+  int face = -1;
+  if (all)
+    for (int i = 0; i < 6; i++) all[i] = -1.0f;
+  for (int i = 0; i < 3; i++) {
+    if (!(fabsf(lv[i]) > MJW_MINVAL)) continue;
+    const int j = (i + 1) % 3, k = (i + 2) % 3;
+    for (int s = 0; s < 2; s++) {
+      const float sol = ((s ? size[i] : -size[i]) - lp[i]) / lv[i];
+      if (!(sol >= 0.0f)) continue;
+      if (fabsf(lp[j] + sol * lv[j]) <= size[j] && fabsf(lp[k] + sol * lv[k]) <= size[k]) {
+        if (x < 0.0f || sol < x) {
+          x = sol;
+          face = 2 * i + s;
+        }
+        if (all) all[2 * i + s] = sol;
+      }
+    }
+  }
+  if (x >= 0.0f) {
+    nl[0] = nl[1] = nl[2] = 0.0f;
+    nl[face >> 1] = (face & 1) ? 1.0f : -1.0f;
+  }
+  return x;
+}
+
+// does the ray meet the box at all (ray_box without the normal; the mesh's bounding-box pre-test)
+__device__ __forceinline__ bool box_test(const float* size, const float* lp, const float* lv) {
+  float n[3];
+  return ray_box(size, lp, lv, n, nullptr) >= 0.0f;
+}
+
+// the primitive types (ray.py:799-820); meshes and heightfields need their data (below)
+__device__ __forceinline__ float ray_geom(int type, const float* size, const float* lp, const float* lv, float* nl) {
+  switch (type) {
+    case RG_PLANE: return ray_plane(size, lp, lv, nl);
+    case RG_SPHERE: return ray_sphere(size[0] * size[0], lp, lv, nl);
+    case RG_CAPSULE: return ray_capsule(size, lp, lv, nl);
+    case RG_ELLIPSOID: return ray_ellipsoid(size, lp, lv, nl);
+    case RG_CYLINDER: return ray_cylinder(size, lp, lv, nl);
+    case RG_BOX: return ray_box(size, lp, lv, nl, nullptr);
+    default: return -1.0f;
+  }
+}
+
+// two unit vectors spanning the plane normal to lv (any such pair serves ray_triangle)
+__device__ __forceinline__ void ray_basis(const float* lv, float* b0, float* b1) {
+  const float ax = fabsf(lv[0]), ay = fabsf(lv[1]), az = fabsf(lv[2]);
+  float e[3] = {0.0f, 0.0f, 0.0f};
+  e[(ax <= ay && ax <= az) ? 0 : (ay <= az ? 1 : 2)] = 1.0f;  // the axis lv leans on least
+  cross3(b0, lv, e);
+  normalize3(b0);
+  cross3(b1, lv, b0);
+  normalize3(b1);
+}
+
+// ray.py:128-184: two-sided triangle; the vertices are projected on (b0, b1), the origin must lie inside the
+// projected triangle (edges included); normal = normalize((v0 - v2) x (v1 - v2)), by the winding
+__device__ __forceinline__ float ray_triangle(const float* v0, const float* v1, const float* v2, const float* lp, const float* lv,
+                                              const float* b0, const float* b1, float* nl) {
+  float px[3], py[3];
+  const float* v[3] = {v0, v1, v2};
+  for (int k = 0; k < 3; k++) {
+    const float d[3] = {v[k][0] - lp[0], v[k][1] - lp[1], v[k][2] - lp[2]};
+    px[k] = dot3(d, b0);
+    py[k] = dot3(d, b1);
+  }
+  if ((px[0] > 0.0f && px[1] > 0.0f && px[2] > 0.0f) || (px[0] < 0.0f && px[1] < 0.0f && px[2] < 0.0f) ||
+      (py[0] > 0.0f && py[1] > 0.0f && py[2] > 0.0f) || (py[0] < 0.0f && py[1] < 0.0f && py[2] < 0.0f))
+    return -1.0f;
+  // s e0 + t e1 = -p2 with e0 = p0 - p2, e1 = p1 - p2
+  const float e0x = px[0] - px[2], e0y = py[0] - py[2], e1x = px[1] - px[2], e1y = py[1] - py[2];
+  const float det = e0x * e1y - e1x * e0y;
+  if (fabsf(det) < MJW_MINVAL) return -1.0f;
+  const float s = (e1x * py[2] - e1y * px[2]) / det;
+  const float t = (e0y * px[2] - e0x * py[2]) / det;
+  if (s < 0.0f || t < 0.0f || s + t > 1.0f) return -1.0f;
+  const float d0[3] = {v0[0] - v2[0], v0[1] - v2[1], v0[2] - v2[2]};
+  const float d1[3] = {v1[0] - v2[0], v1[1] - v2[1], v1[2] - v2[2]};
+  const float dp[3] = {lp[0] - v2[0], lp[1] - v2[1], lp[2] - v2[2]};
+  float n[3];
+  cross3(n, d0, d1);
+  const float den = dot3(lv, n);
+  if (fabsf(den) < MJW_MINVAL) return -1.0f;
+  const float x = -dot3(dp, n) / den;
+  if (!(x >= 0.0f)) return -1.0f;
+  normalize3(n);
+  nl[0] = n[0]; nl[1] = n[1]; nl[2] = n[2];
+  return x;
+}
+
+// ray.py:451-619: heightfield = the base box (z in [-size[3], 0]), the surface triangles of the cells under
+// the ray's segment through the top box (z in [0, size[2]]), and the four side walls below the elevation
+// profile.  hsize = hfield_size (x, y half extents, top, base); data = the nrow x ncol elevations in [0, 1].
+__device__ __forceinline__ float ray_hfield(const float* hsize, int nrow, int ncol, const float* data, const float* lp, const float* lv,
+                                            float* nl) {
+  const float sx = hsize[0], sy = hsize[1], top = hsize[2], base = hsize[3];
+  const float bsize[3] = {sx, sy, 0.5f * base}, tsize[3] = {sx, sy, 0.5f * top};
+  const float lpb[3] = {lp[0], lp[1], lp[2] + 0.5f * base}, lpt[3] = {lp[0], lp[1], lp[2] - 0.5f * top};
+  float all[6], nt[3];
+  float x = ray_box(bsize, lpb, lv, nl, nullptr);
+  const float xt = ray_box(tsize, lpt, lv, nt, all);
+  if (xt < 0.0f) return x;
+
+  float b0[3], b1[3];
+  ray_basis(lv, b0, b1);
+  // the part of the ray inside the top box
+  float seg0 = 0.0f, seg1 = xt;
+  for (int i = 0; i < 6; i++)
+    if (all[i] > seg1) {
+      seg0 = xt;
+      seg1 = all[i];
+    }
+  const float dx = safe_div(2.0f * sx, (float)(ncol - 1)), dy = safe_div(2.0f * sy, (float)(nrow - 1));
+  const float cx0 = safe_div(lp[0] + seg0 * lv[0] + sx, dx), cx1 = safe_div(lp[0] + seg1 * lv[0] + sx, dx);
+  const float cy0 = safe_div(lp[1] + seg0 * lv[1] + sy, dy), cy1 = safe_div(lp[1] + seg1 * lv[1] + sy, dy);
+  // cell ranges with one cell of padding, clamped before the conversion to int
+  const float fc = (float)(ncol - 1), fr = (float)(nrow - 1);
+  const int cmin = (int)fmaxf(0.0f, fminf(fc, floorf(fminf(cx0, cx1)) - 1.0f));
+  const int cmax = (int)fminf(fc, fmaxf(0.0f, ceilf(fmaxf(cx0, cx1)) + 1.0f));
+  const int rmin = (int)fmaxf(0.0f, fminf(fr, floorf(fminf(cy0, cy1)) - 1.0f));
+  const int rmax = (int)fminf(fr, fmaxf(0.0f, ceilf(fmaxf(cy0, cy1)) + 1.0f));
+  for (int r = rmin; r < rmax; r++) {
+    for (int c = cmin; c < cmax; c++) {
+      const float xa = dx * (float)c - sx, xb = dx * (float)(c + 1) - sx;
+      const float ya = dy * (float)r - sy, yb = dy * (float)(r + 1) - sy;
+      const float v00[3] = {xa, ya, data[r * ncol + c] * top};
+      const float v10[3] = {xb, ya, data[r * ncol + c + 1] * top};
+      const float v11[3] = {xb, yb, data[(r + 1) * ncol + c + 1] * top};
+      const float v01[3] = {xa, yb, data[(r + 1) * ncol + c] * top};
+      float n[3];
+      float sol = ray_triangle(v00, v10, v11, lp, lv, b0, b1, n);
+      if (sol >= 0.0f && (x < 0.0f || sol < x)) {
+        x = sol;
+        nl[0] = n[0]; nl[1] = n[1]; nl[2] = n[2];
+      }
+      sol = ray_triangle(v00, v11, v01, lp, lv, b0, b1, n);
+      if (sol >= 0.0f && (x < 0.0f || sol < x)) {
+        x = sol;
+        nl[0] = n[0]; nl[1] = n[1]; nl[2] = n[2];
+      }
+    }
+  }
+  // side walls: the x faces (0: -x, 1: +x) and y faces (2: -y, 3: +y) of the top box, where the hit lies
+  // below the elevation profile along that edge
+  for (int i = 0; i < 4; i++) {
+    if (!(all[i] >= 0.0f && (all[i] < x || x < 0.0f))) continue;
+    const float z = safe_div(lp[2] + all[i] * lv[2], top);
+    float y, y0, z0, z1;
+    if (i < 2) {
+      y = safe_div(lp[1] + all[i] * lv[1] + sy, dy);
+      y0 = fmaxf(0.0f, fminf((float)(nrow - 2), floorf(y)));
+      const int k = (int)y0, c = i == 1 ? ncol - 1 : 0;
+      z0 = data[k * ncol + c];
+      z1 = data[(k + 1) * ncol + c];
+    } else {
+      y = safe_div(lp[0] + all[i] * lv[0] + sx, dx);
+      y0 = fmaxf(0.0f, fminf((float)(ncol - 2), floorf(y)));
+      const int k = (int)y0, r = i == 3 ? nrow - 1 : 0;
+      z0 = data[r * ncol + k];
+      z1 = data[r * ncol + k + 1];
+    }
+    if (z < z0 * (y0 + 1.0f - y) + z1 * (y - y0)) {
+      x = all[i];
+      nl[0] = (float)(i == 1) - (float)(i == 0);
+      nl[1] = (float)(i == 3) - (float)(i == 2);
+      nl[2] = 0.0f;
+    }
+  }
+  return x;
+}
+
+}  // namespace ray
+}  // namespace mjw

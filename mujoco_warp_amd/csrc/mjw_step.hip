@@ -3645,6 +3645,13 @@ int step(const mjw_model_t* m, const mjw_data_t* d, void* stream, const char* na
 MJW_PROF_READER(mjw_prof_read)
 MJW_WLOG_SETTER(mjw_prof_wlog_fwd)
 
+namespace mjw {
+int set_last_error(int code, const char* msg) {
+  g_err = msg;
+  return code;
+}
+}  // namespace mjw
+
 extern "C" {
 
 int mjw_abi_version(void) { return MJW_ABI_VERSION; }

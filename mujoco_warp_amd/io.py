@@ -441,6 +441,18 @@ def put_model(mjm, device=None) -> types.Model:
                "eq_active0", "body_mocapid"):
     if hasattr(mjm, name):
       setattr(m, name, _i32(np.asarray(getattr(mjm, name)), dev))
+  # ray casting (ray.py; the side struct mjw_ray_model_t is built from these at call time): visibility and
+  # group of each geom, material colours, mesh triangles; geom_rgba / mat_rgba are batchable per world
+  ng = int(mjm.ngeom)
+  m.nmat = int(getattr(mjm, "nmat", 0))
+  m.nmeshface = int(getattr(mjm, "nmeshface", 0))
+  m.geom_group = _i32(np.asarray(getattr(mjm, "geom_group", np.zeros(ng))), dev)
+  m.geom_matid = _i32(np.asarray(getattr(mjm, "geom_matid", -np.ones(ng))).reshape(-1)[:ng], dev)
+  m.geom_rgba = _f32(np.asarray(getattr(mjm, "geom_rgba", np.tile([0.5, 0.5, 0.5, 1.0], (ng, 1))), dtype=np.float64).reshape(1, ng, 4), dev)
+  m.mat_rgba = _f32(np.asarray(getattr(mjm, "mat_rgba", np.zeros((0, 4))), dtype=np.float64).reshape(1, m.nmat, 4), dev)
+  m.mesh_face = _i32(np.asarray(getattr(mjm, "mesh_face", np.zeros((0, 3)))).reshape(m.nmeshface, 3), dev)
+  m.mesh_faceadr = _i32(np.asarray(getattr(mjm, "mesh_faceadr", np.zeros(0))), dev)
+  m.mesh_facenum = _i32(np.asarray(getattr(mjm, "mesh_facenum", np.zeros(0))), dev)
   m._mjm_sizes = dict(nq=mjm.nq, nv=nv)
   return m
 

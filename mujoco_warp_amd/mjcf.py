@@ -997,6 +997,7 @@ class _Compiler:
 
     self._load_meshes(root)
     self._load_hfields(root)
+    self._load_materials(root)
     self._build_geoms()
     self._build_inertia()
     self._build_sites_cams_lights()
@@ -1045,6 +1046,11 @@ class _Compiler:
     m.mesh_vertadr = np.concatenate([[0], np.cumsum(m.mesh_vertnum)[:-1]]).astype(np.int32) if m.nmesh else np.zeros(0, np.int32)
     m.mesh_vert = np.concatenate([v for v, _ in self.mesh_data]) if m.nmesh else np.zeros((0, 3))
     m.nmeshvert = int(m.mesh_vertnum.sum())
+    # triangles (MuJoCo's mesh_face): vertex indices local to the mesh, after the duplicate-vertex remap
+    m.mesh_facenum = np.array([len(f) for _, f in self.mesh_data], dtype=np.int32)
+    m.mesh_faceadr = np.concatenate([[0], np.cumsum(m.mesh_facenum)[:-1]]).astype(np.int32) if m.nmesh else np.zeros(0, np.int32)
+    m.mesh_face = (np.concatenate([np.asarray(f).reshape(-1, 3) for _, f in self.mesh_data]) if m.nmesh else np.zeros((0, 3))).astype(np.int32)
+    m.nmeshface = int(m.mesh_facenum.sum())
     # per-vertex normals (MuJoCo's mesh_normal without tangent frames: normalnum = vertnum): the
     # area-weighted mean of the adjacent triangles' normals, in the mesh frame (mesh_quat identity: this
     # compiler keeps mesh vertices in their file frame)
@@ -1067,6 +1073,20 @@ class _Compiler:
     m.mesh_polymapadr = np.concatenate([[0], np.cumsum(m.mesh_polymapnum)[:-1]]).astype(np.int32) if pmaps else np.zeros(0, np.int32)
     m.mesh_polymap = np.array([i for mp in pmaps for i in mp], dtype=np.int32)
     m.nmeshpoly, m.nmeshpolyvert, m.nmeshpolymap = len(loops), len(m.mesh_polyvert), len(m.mesh_polymap)
+
+  def _load_materials(self, root):
+    """<asset><material>: only the colour (mat_rgba, MuJoCo's default 1 1 1 1) is kept -- ray casting skips
+    geoms whose material is fully transparent."""
+    m = self.m
+    self.mat_id = {}
+    rgba = []
+    for asset in root.findall("asset"):
+      for el in asset.findall("material"):
+        a = self._resolve("material", el, None)
+        self.mat_id[a.get("name", "")] = len(rgba)
+        rgba.append(_floats(a.get("rgba", "1 1 1 1"), 4))
+    m.nmat = len(rgba)
+    m.mat_rgba = np.array(rgba, dtype=np.float64).reshape(-1, 4)
 
   def _load_hfields(self, root):
     """<asset><hfield>: nrow x ncol elevation grid (row 0 at -y, MuJoCo's mjModel.hfield_data order), size =
@@ -1286,7 +1306,8 @@ class _Compiler:
     self.geom_mesh_props = [(r["mesh_com"], r["mesh_I"]) for r in rows]
     m.geom_mass_ = np.array([r["mass"] for r in rows])
     m.geom_inertia_ = np.array([r["inertia"] for r in rows]).reshape(ng, 3)
-    m.geom_rgba = np.tile([0.5, 0.5, 0.5, 1.0], (ng, 1))
+    m.geom_rgba = np.array([r["rgba"] for r in rows], dtype=np.float64).reshape(ng, 4)
+    m.geom_matid = np.array([r["matid"] for r in rows], dtype=np.int32)
     body_geomadr = -np.ones(m.nbody, dtype=np.int32)
     body_geomnum = np.zeros(m.nbody, dtype=np.int32)
     for g, r in enumerate(rows):
@@ -1372,6 +1393,11 @@ class _Compiler:
       size = 0.5 * (hi - lo)
     else:
       raise NotImplementedError(gtype)
+    matid = -1
+    if ga.get("material"):
+      if ga["material"] not in self.mat_id:
+        raise ValueError(f"geom {ga.get('name', '')}: unknown material '{ga['material']}'")
+      matid = self.mat_id[ga["material"]]
     density = float(ga.get("density", _GEOM_DEFAULTS["density"]))
     mass = float(ga["mass"]) if "mass" in ga else density * vol
     fluid = _geom_fluid(ga, gtype, size)
@@ -1390,6 +1416,8 @@ class _Compiler:
       condim=int(ga.get("condim", 3)),
       priority=int(ga.get("priority", 0)),
       group=int(ga.get("group", 0)),
+      rgba=_floats(ga.get("rgba", "0.5 0.5 0.5 1"), 4),
+      matid=matid,
       size=size,
       pos=pos,
       quat=quat,

@@ -1,0 +1,125 @@
+"""Batched ray casting over all geom types (mujoco_warp/_src/ray.py:1168-1312 `ray` / `rays`).
+
+One HIP launch (`mjw_rays`, csrc/mjw_ray.hip) on the Data's stream: for every world and ray the nearest geom
+along `pnt + x vec`, x >= 0, at the frames `d.geom_xpos` / `d.geom_xmat` the last position stage left (no
+kinematics run here, so it serves dense and sparse models alike).  There is no BVH or render context in this
+build: `rc` other than None is refused, and flex elements are not hit (as on the reference's path without
+`rc`).  Meshes are brute force over their triangles.
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib
+from .types import Data, Model
+
+
+def _ray_model(m: Model) -> _lib.CRayModel:
+  """The side struct mjw_ray_model_t from the Model's current tensors (built per call: a caller may have
+  replaced geom_rgba / mat_rgba with per-world batches)."""
+  ng, nmat, nface = int(m.ngeom), int(m.nmat), int(m.nmeshface)
+
+  def chk(name, dtype, numel=None, per_batch=None):
+    t = getattr(m, name)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != m.geom_type.device:
+      raise ValueError(f"model field {name}: a contiguous {dtype} tensor on {m.geom_type.device}")
+    if numel is not None and t.numel() != numel:
+      raise ValueError(f"model field {name}: expected {numel} values, got shape {tuple(t.shape)}")
+    if per_batch is not None and (t.dim() < 1 or t.shape[0] < 1 or t.numel() != t.shape[0] * per_batch):
+      raise ValueError(f"model field {name}: expected (nb, {per_batch}) values, got shape {tuple(t.shape)}")
+    return t
+
+  c = _lib.CRayModel()
+  c.ngeom, c.nmat, c.nmeshface = ng, nmat, nface
+  c.geom_group = chk("geom_group", torch.int32, ng).data_ptr()
+  c.geom_matid = chk("geom_matid", torch.int32, ng).data_ptr()
+  rgba = chk("geom_rgba", torch.float32, per_batch=ng * 4)
+  c.geom_rgba, c.geom_rgba_nb = rgba.data_ptr(), int(rgba.shape[0])
+  mat = chk("mat_rgba", torch.float32, per_batch=nmat * 4)
+  c.mat_rgba, c.mat_rgba_nb = mat.data_ptr(), int(mat.shape[0])
+  c.mesh_face = chk("mesh_face", torch.int32, nface * 3).data_ptr()
+  c.mesh_faceadr = chk("mesh_faceadr", torch.int32).data_ptr()
+  c.mesh_facenum = chk("mesh_facenum", torch.int32).data_ptr()
+  c._keep = (rgba, mat)  # the tensors whose pointers the struct holds
+  return c
+
+
+def _check(name, t, dtype, shape, device):
+  if not isinstance(t, torch.Tensor):
+    raise ValueError(f"rays: {name} must be a torch tensor")
+  if t.dtype != dtype:
+    raise ValueError(f"rays: {name} must be {dtype}, got {t.dtype}")
+  if tuple(t.shape) != tuple(shape):
+    raise ValueError(f"rays: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+  if t.device != device:
+    raise ValueError(f"rays: {name} is on {t.device}, the Data is on {device}")
+  if not t.is_contiguous():
+    raise ValueError(f"rays: {name} must be contiguous")
+
+
+def rays(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Optional[Sequence[int]], flg_static: bool,
+         bodyexclude: torch.Tensor, dist: torch.Tensor, geomid: torch.Tensor, normal: torch.Tensor, rc=None) -> None:
+  """Ray intersections for every world and ray (ray.py:1212-1312).
+
+  pnt, vec: float32 (nb, nray, 3), nb = 1 or nworld (world w reads row w % nb); vec is not normalised and
+  `dist` is in units of |vec|.  geomgroup: None or six ints (all -1 / None: no filter; else a geom is skipped
+  when geomgroup[clamp(geom_group, 0, 5)] == 0).  flg_static False skips geoms of bodies welded to the world.
+  bodyexclude: int32 (nray,), geoms of that body are skipped (-1: none).  Geoms with alpha 0 (their
+  material's when they have one, else their own rgba) are skipped.  Outputs: dist float32 (nworld, nray),
+  geomid int32 (nworld, nray), normal float32 (nworld, nray, 3); a miss gives -1, -1, 0, and equal distances
+  go to the lowest geom id."""
+  if rc is not None:
+    raise NotImplementedError("rays: render contexts (BVH acceleration) are not part of this build; pass rc=None")
+  dev = d.qpos.device
+  nworld = int(d.nworld)
+  if not isinstance(pnt, torch.Tensor) or pnt.dim() != 3 or pnt.shape[2] != 3:
+    raise ValueError("rays: pnt must be a float32 tensor of shape (nb, nray, 3)")
+  nb, nray = int(pnt.shape[0]), int(pnt.shape[1])
+  if nb != 1 and nb != nworld:
+    raise ValueError(f"rays: pnt / vec batch must be 1 or nworld = {nworld}, got {nb}")
+  _check("pnt", pnt, torch.float32, (nb, nray, 3), dev)
+  if not isinstance(vec, torch.Tensor) or vec.dim() != 3 or (int(vec.shape[0]) != 1 and int(vec.shape[0]) != nworld):
+    raise ValueError(f"rays: vec must have shape (nb, {nray}, 3) with nb = 1 or nworld = {nworld}")
+  _check("vec", vec, torch.float32, (int(vec.shape[0]), nray, 3), dev)
+  _check("bodyexclude", bodyexclude, torch.int32, (nray,), dev)
+  _check("dist", dist, torch.float32, (nworld, nray), dev)
+  _check("geomid", geomid, torch.int32, (nworld, nray), dev)
+  _check("normal", normal, torch.float32, (nworld, nray, 3), dev)
+  group = None
+  if geomgroup is not None:
+    g = [int(x) for x in geomgroup]
+    if len(g) != 6:
+      raise ValueError(f"rays: geomgroup must be None or six ints, got {len(g)}")
+    group = (ctypes.c_int * 6)(*g)
+  rm = _ray_model(m)
+  if nray == 0:
+    return
+  from .forward import _stream
+  from .io import cdata, cmodel
+
+  L = _lib.lib()
+  rcode = L.mjw_rays(cmodel(m), cdata(d), ctypes.byref(rm), pnt.data_ptr(), nb, vec.data_ptr(), int(vec.shape[0]), nray, group,
+                     int(bool(flg_static)), bodyexclude.data_ptr(), dist.data_ptr(), geomid.data_ptr(), normal.data_ptr(), _stream(d))
+  _lib.check(rcode, "mjw_rays")
+
+
+def ray(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Optional[Sequence[int]] = None, flg_static: bool = True,
+        bodyexclude: int = -1, rc=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+  """One ray per world (ray.py:1168-1209): pnt, vec of shape (nb, 1, 3) with nb = 1 (the same ray in every
+  world) or nworld.  Returns dist (nworld, 1), geomid (nworld, 1), normal (nworld, 1, 3)."""
+  if rc is not None:
+    raise NotImplementedError("ray: render contexts (BVH acceleration) are not part of this build; pass rc=None")
+  if not isinstance(pnt, torch.Tensor) or pnt.dim() != 3 or pnt.shape[1] != 1:
+    raise ValueError("ray: pnt must have shape (nb, 1, 3)")
+  dev = d.qpos.device
+  nworld = int(d.nworld)
+  excl = torch.full((1,), int(bodyexclude), dtype=torch.int32, device=dev)
+  dist = torch.empty((nworld, 1), dtype=torch.float32, device=dev)
+  geomid = torch.empty((nworld, 1), dtype=torch.int32, device=dev)
+  normal = torch.empty((nworld, 1, 3), dtype=torch.float32, device=dev)
+  rays(m, d, pnt, vec, geomgroup, flg_static, excl, dist, geomid, normal)
+  return dist, geomid, normal
