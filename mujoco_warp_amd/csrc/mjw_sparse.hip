@@ -334,34 +334,39 @@ __device__ void com_pos(const mjw_model_t& m, const mjw_data_t& d, int wid, Smem
   // 1.5e-5 of the oracle's fp64 value and sat on the critical path of the whole block
   constexpr int BIG = 64, NBIG = 16;
   __shared__ int big[NBIG];
-  __shared__ int nbig;
-  if (tid() == 0) nbig = 0;
-  __syncthreads();
   for (int b = tid(); b < nb; b += BLK) {
-    if (m.body_subtree_end[b] - b > BIG) {  // (past NBIG of them: serial here after all)
-      const int k = atomicAdd(&nbig, 1);
-      if (k < NBIG) {
-        big[k] = b;
-        continue;
-      }
-    }
+    if (m.body_subtree_end[b] - b > BIG) continue;
     float s[3] = {0.0f, 0.0f, 0.0f};
     for (int c = b; c < m.body_subtree_end[b]; c++)
       for (int i = 0; i < 3; i++) s[i] += xipos[3 * c + i] * body_mass[c];
     const float mass = body_subtreemass[b];
     for (int i = 0; i < 3; i++) sc[3 * b + i] = mass != 0.0f ? s[i] / mass : s[i];
   }
-  __syncthreads();
-  const int nbg = min(nbig, NBIG);
-  for (int j = 0; j < nbg; j++) {  // uniform: the big subtrees, one block sum each
-    const int b = big[j], e = m.body_subtree_end[b];
-    float v[3] = {0.0f, 0.0f, 0.0f};
-    for (int c = b + tid(); c < e; c += BLK)
-      for (int i = 0; i < 3; i++) v[i] += xipos[3 * c + i] * body_mass[c];
-    block_sum<3>(v, sm);
-    const float mass = body_subtreemass[b];
-    if (tid() == 0)
-      for (int i = 0; i < 3; i++) sc[3 * b + i] = mass != 0.0f ? v[i] / mass : v[i];
+  // the big subtrees in body order, NBIG block sums per round.  A scan hands out the slots: which subtree
+  // gets a block sum must not depend on the order the waves arrive in (an LDS atomic did this before; past
+  // NBIG big subtrees two replicas of a world could differ, and a subtree of hundreds of bodies that lost
+  // its slot was summed serially after all)
+  for (int base = 0; base < nb; base += BLK) {  // uniform
+    const int bb = base + tid();
+    const int isbig = bb < nb && m.body_subtree_end[bb] - bb > BIG;
+    int total;
+    const int off = block_scan(isbig, total, sm);
+    for (int lo = 0; lo < total; lo += NBIG) {
+      __syncthreads();
+      if (isbig && off >= lo && off < lo + NBIG) big[off - lo] = bb;
+      __syncthreads();
+      const int nbg = min(NBIG, total - lo);
+      for (int j = 0; j < nbg; j++) {  // uniform: one block sum each
+        const int b = big[j], e = m.body_subtree_end[b];
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        for (int c = b + tid(); c < e; c += BLK)
+          for (int i = 0; i < 3; i++) v[i] += xipos[3 * c + i] * body_mass[c];
+        block_sum<3>(v, sm);
+        const float mass = body_subtreemass[b];
+        if (tid() == 0)
+          for (int i = 0; i < 3; i++) sc[3 * b + i] = mass != 0.0f ? v[i] / mass : v[i];
+      }
+    }
   }
   __syncthreads();
   const float* body_inertia = MR(body_inertia);

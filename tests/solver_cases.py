@@ -54,8 +54,9 @@ QPOS_TOL, QVEL_TOL = 1e-5, 5e-3  # one step against the fp64 oracle (test_solve_
 LADDER = (3, 4, 8, 9, 16, 17, 31, 32, 33, 63, 64, 65)
 
 
-def ladder_xml(nfeet, nhinge, solver, bare=False, eulerdamp=True, jacobian="dense"):
-  """MJCF of the ladder model: nv = 3 nfeet + nhinge, no tendons / actuators / sensors / boxes."""
+def ladder_xml(nfeet, nhinge, solver, bare=False, eulerdamp=True, jacobian="dense", armature="0.01", dz=DZ):
+  """MJCF of the ladder model: nv = 3 nfeet + nhinge, no tendons / actuators / sensors / boxes; `armature` of the hinges,
+  `dz` between the spheres of a foot."""
   flag = "" if eulerdamp else '<flag eulerdamp="disable"/>'
   s = [f'<mujoco><compiler angle="radian"/><option timestep="0.002" cone="pyramidal" solver="{solver}" jacobian="{jacobian}">{flag}</option>'
        '<worldbody><geom type="plane" size="20 20 .1"/>']
@@ -63,7 +64,7 @@ def ladder_xml(nfeet, nhinge, solver, bare=False, eulerdamp=True, jacobian="dens
     s.append(f'<body pos="{b * 0.6} 0 0"><joint name="fx{b}" type="slide" axis="1 0 0"/><joint name="fy{b}" type="slide" axis="0 1 0"/>'
              f'<joint name="fz{b}" type="slide" axis="0 0 1"/>')
     for k in (3, 2, 1, 0):  # the lowest sphere last: a foot's last contact is its deepest, the one that carries the load
-      s.append(f'<geom type="sphere" size="{R}" pos="{0.12 * (k % 2)} {0.12 * (k // 2)} {k * DZ}" condim="3" mass="0.3"/>')
+      s.append(f'<geom type="sphere" size="{R}" pos="{0.12 * (k % 2)} {0.12 * (k // 2)} {k * dz}" condim="3" mass="0.3"/>')
     s.append("</body>")
   h = chain = 0
   while h < nhinge:
@@ -73,7 +74,7 @@ def ladder_xml(nfeet, nhinge, solver, bare=False, eulerdamp=True, jacobian="dens
       fl = ' frictionloss="0.3"' if (h < 2 and not bare) else ""
       if k:
         s.append('<body pos="0.2 0 0">')
-      s.append(f'<joint name="h{h}" type="hinge" axis="0 1 0" limited="true" range="-0.5 0.5" armature="0.01" damping="0.1"{fl}/>'
+      s.append(f'<joint name="h{h}" type="hinge" axis="0 1 0" limited="true" range="-0.5 0.5" armature="{armature}" damping="0.1"{fl}/>'
                '<geom type="capsule" size="0.02" fromto="0 0 0 0.2 0 0" contype="0" conaffinity="0"/>')
       h += 1
     s.append("</body>" * n)
@@ -91,7 +92,7 @@ def ladder_counts(mjm):
   return (mjm.nv - nhinge) // 3, nhinge, int(mjm.neq), int((np.asarray(mjm.dof_frictionloss) > 0).sum())
 
 
-def ladder_state(mjm, target_nefc, rng, njmax=None):
+def ladder_state(mjm, target_nefc, rng, njmax=None, dz=DZ):
   """qpos, qvel with ne + nf + 4 contacts + limits = target_nefc rows: as many contacts as fit, limits make
   up the remainder.  The frictionloss hinges and the equality's second joint take a limit row only when no
   other hinge is left (the (4, 4) model).  qvel ~ N(0, 0.3), except that the foot whose contact owns the last
@@ -113,7 +114,7 @@ def ladder_state(mjm, target_nefc, rng, njmax=None):
     k = min(4, c)
     c -= k
     if k:  # spheres 0 .. k-1 penetrate, the topmost of them by DZ / 2; sphere k clears the plane by DZ / 2
-      qpos[3 * b + 2] = R - (k - 0.5) * DZ
+      qpos[3 * b + 2] = R - (k - 0.5) * dz
   if ne or nf:
     first = [h for h in range(nhinge) if h >= nf and h != nhinge - 2]
     last = [nhinge - 2] + list(range(nf))
