@@ -19,6 +19,7 @@
  *   mjw_sensor            <- sensor.sensor_pos/_vel/_acc  sensor.py:761,1377,2447
  *   mjw_ctrl_noise        <- benchmark.ctrl_noise         _src/benchmark.py:41-83
  *   mjw_rays              <- ray.rays (no render context) ray.py:1212-1312
+ *   mjw_inverse           <- inverse.inverse's constraint + combine  inverse.py, solver.py init_context(grad=False)
  *
  * Ownership: the caller owns every buffer (device pointers below); the library
  * never allocates or frees device memory and keeps no global mutable state.
@@ -34,7 +35,7 @@
 
 #include <stdint.h>
 
-#define MJW_ABI_VERSION 35
+#define MJW_ABI_VERSION 36
 
 /* ---- model: int scalars ---- */
 #define MJW_MODEL_INT_SCALARS(X)                                                                   \
@@ -141,7 +142,8 @@
  * world's contact-pool range (first slot, count / span): the sparse path's, and the dense contact-rows pass's;
  * sp_idx16 holds the CG's 16-bit copies of efc_J_colind and of the transposed index's rows (two uint16 per int).
  * world_order / world_key: the dense path's longest-first world order (a permutation of the worlds, rebuilt
- * every step from the previous step's solver iterations) and each world's iteration bucket. */
+ * every step from the previous step's solver iterations) and each world's iteration bucket.
+ * qfrc_inverse: the inverse dynamics force mjw_inverse writes (ABI 36). */
 #define MJW_DATA_REAL_ARRAYS(X)                                                                    \
   X(time, 1) X(qpos, nq) X(qvel, nv) X(act, na) X(ctrl, nu) X(qacc_warmstart, nv)                 \
   X(qfrc_applied, nv) X(xfrc_applied, nbody * 6) X(mocap_pos, nmocap * 3) X(mocap_quat, nmocap * 4) \
@@ -165,7 +167,8 @@
   X(flexedge_J, nflexedge * 6) X(flex_frc, nflexelem * 12 + nflexedge * 12)                       \
   X(sp_body, nbody * 6) X(sp_vec, nv * 10) X(sp_row, njmax * 3) X(sp_LD, nM) X(sp_H, sp_nH * sp_nH) \
   X(efc_JT_val, njmax_pad * njrow)                                                                 \
-  X(ten_length, ntendon) X(ten_velocity, ntendon) X(ten_J, nJten)
+  X(ten_length, ntendon) X(ten_velocity, ntendon) X(ten_J, nJten)                                 \
+  X(qfrc_inverse, nv)
 
 /* ---- data: int arrays, (nworld, count) ---- */
 #define MJW_DATA_INT_ARRAYS(X)                                                                     \
@@ -356,6 +359,19 @@ int mjw_primitive_narrowphase(const mjw_model_t* m, const mjw_data_t* d, const i
 int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb, const float* vec,
              int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude, float* dist, int* geomid,
              float* normal, void* stream);
+
+/* Inverse dynamics at the caller's acceleration (inverse.py `inverse`, its constraint and combine steps; ABI 36):
+ * with the position and velocity stages of the current state in `d` (qM, qfrc_bias, qfrc_passive and the constraint
+ * rows), one launch evaluates the row law once at d->qacc, which it only reads.  Over the rows r < n = min(nefc, njmax):
+ * Jaref = J qacc - aref, efc_force and efc_state from the row law (equality, friction loss, limit, frictionless,
+ * pyramidal and elliptic rows; an elliptic contact whose rows njmax cuts contributes nothing), then
+ * qfrc_constraint = J' efc_force, efc_Ma = M qacc and
+ * qfrc_inverse = qfrc_bias + efc_Ma - qfrc_passive - qfrc_constraint.  Rows r >= n of efc_force / efc_state are left
+ * alone; without rows (njmax == 0, the constraint disable flag, no active row) qfrc_constraint is exactly zero.
+ * Sparse models also use sp_row and the transposed-index workspace (efc_JT_*, sp_idx16, sp_cnt), as mjw_solve does.
+ * nworld <= 0 is a successful no-op without a launch; null model / data / arrays give -1, a dense-path model with
+ * nv > 64 gives -2. */
+int mjw_inverse(const mjw_model_t* m, const mjw_data_t* d, void* stream);
 
 #ifdef __cplusplus
 }

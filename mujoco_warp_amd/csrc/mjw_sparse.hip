@@ -3197,6 +3197,171 @@ __device__ __forceinline__ float linesearch(const mjw_model_t& m, SolveCtx& c, i
   return alpha;
 }
 
+// The transposed index of J (CSR by dof: JT_adr, rows JT16, values JT_val; counts, scan, fill, per-column
+// sort: a fixed summation order of J'f), the 16-bit columns Jcol16, and Jaref = J x - aref on the way.
+// `cnt` (nv + 1 column counters) must be zero and visible to the block on entry.
+__device__ __forceinline__ void build_transpose(const mjw_model_t& m, const SolveCtx& c, const float* x, int* cnt, int* JT_adr, int* JT_ind,
+                                                float* JT_val, unsigned short* Jcol16, unsigned short* JT16, Smem& sm) {
+  const int nv = c.nv;
+  const long P = c.P;
+  for (int r = tid(); r < c.nefc; r += nthr())
+    for (int k = 0; k < c.Jnnz[r]; k++) atomicAdd(&cnt[c.Jcol[k * P + r]], 1);
+  __syncthreads();
+  int run = 0;
+  for (int c0 = 0; c0 < nv; c0 += nthr()) {
+    const int i = c0 + tid();
+    const int n = i < nv ? cnt[i] : 0;
+    int chunk;
+    const int off = block_scan(n, chunk, sm);
+    if (i < nv) { JT_adr[i] = run + off; cnt[i] = run + off; }
+    run += chunk;
+  }
+  if (tid() == 0) JT_adr[nv] = run;
+  __syncthreads();
+  // fill carries the values (and computes Jaref on the way); the per-column sort of the
+  // (row * njrow + slot) codes then fixes the summation order of J'f whatever the atomics did
+  for (int r = tid(); r < c.nefc; r += nthr()) {
+    float s = 0.0f;
+    for (int k = 0; k < c.Jnnz[r]; k++) {
+      const float v = c.J[k * P + r];
+      const int col = c.Jcol[k * P + r];
+      Jcol16[k * P + r] = (unsigned short)col;
+      const int pos = atomicAdd(&cnt[col], 1);
+      JT_ind[pos] = r * m.njrow + k;
+      JT_val[pos] = v;
+      s += v * x[col];
+    }
+    c.Jaref[r] = s - c.aref[r];
+  }
+  __syncthreads();
+  for (int i = tid(); i < nv; i += nthr()) {
+    const int a = JT_adr[i], b = JT_adr[i + 1];
+    if (b - a <= SORTN) {
+      // short segment: loaded at once, odd-even transposition network in registers
+      const int n = b - a;
+      int key[SORTN];
+      float val[SORTN];
+#pragma unroll
+      for (int j = 0; j < SORTN; j++) {
+        key[j] = j < n ? JT_ind[a + j] : 0x7fffffff;
+        val[j] = j < n ? JT_val[a + j] : 0.0f;
+      }
+#pragma unroll
+      for (int r = 0; r < SORTN; r++) {
+#pragma unroll
+        for (int j = r & 1; j + 1 < SORTN; j += 2) {
+          const bool sw = key[j] > key[j + 1];
+          const int k0 = key[j], k1 = key[j + 1];
+          const float v0 = val[j], v1 = val[j + 1];
+          key[j] = sw ? k1 : k0;
+          key[j + 1] = sw ? k0 : k1;
+          val[j] = sw ? v1 : v0;
+          val[j + 1] = sw ? v0 : v1;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < SORTN; j++)
+        if (j < n) {
+          JT16[a + j] = (unsigned short)(key[j] / m.njrow);  // code -> row
+          JT_val[a + j] = val[j];
+        }
+      continue;
+    }
+    for (int p = a + 1; p < b; p++) {
+      const int key = JT_ind[p];
+      const float kv = JT_val[p];
+      int q = p - 1;
+      while (q >= a && JT_ind[q] > key) { JT_ind[q + 1] = JT_ind[q]; JT_val[q + 1] = JT_val[q]; q--; }
+      JT_ind[q + 1] = key;
+      JT_val[q + 1] = kv;
+    }
+    for (int p = a; p < b; p++) JT16[p] = (unsigned short)(JT_ind[p] / m.njrow);  // code -> row
+  }
+}
+
+// Inverse dynamics at the caller's qacc (inverse.py `inverse`, its constraint and combine steps), one launch:
+// Ma = M qacc, the transposed index and Jaref = J qacc - aref as solve_kernel<0> builds them, one pass of
+// update_constraint (efc_force, qfrc_constraint = J'f in the index's fixed order), the states, and
+// qfrc_inverse = qfrc_bias + Ma - qfrc_passive - qfrc_constraint.  d.qacc is only read; rows >= min(nefc, njmax)
+// of efc_force / efc_state are left alone; without rows qfrc_constraint is exactly zero.
+template <bool ELL>
+__global__ void __launch_bounds__(BLK) inverse_kernel(const mjw_model_t m, const mjw_data_t d) {
+  __shared__ Smem sm;
+  extern __shared__ int s_cnt[];
+  const int wid = blockIdx.x;
+  const int nv = m.nv, njmax = d.njmax;
+  const float* qacc = d.qacc + (long)wid * nv;
+  float* Ma = d.efc_Ma + (long)wid * nv;
+  float* qfrc_c = d.qfrc_constraint + (long)wid * nv;
+  mul_m_trees(m, d.qM + (long)wid * m.nM, qacc, Ma);
+  const bool rows = njmax > 0 && !(m.opt_disableflags & DSBL_CONSTRAINT);
+  const int nefc = rows ? min(d.nefc[wid], njmax) : 0;
+  if (nefc == 0) {
+    for (int i = tid(); i < nv; i += nthr()) qfrc_c[i] = 0.0f;
+  } else {
+    SolveCtx c;
+    c.rphase = 0;
+    c.nv = nv;
+    c.nefc = nefc;
+    c.ne = d.ne[wid];
+    c.nf = d.nf[wid];
+    c.njrow = m.njrow;
+    const long P = d.njmax_pad;
+    c.P = (int)P;
+    c.J = d.efc_J + (long)wid * P * m.njrow;
+    c.Jcol = d.efc_J_colind + (long)wid * P * m.njrow;
+    c.Jnnz = d.efc_J_rownnz + (long)wid * njmax;
+    int* JT_adr = d.efc_JT_adr + (long)wid * (nv + 1);
+    int* JT_ind = d.efc_JT_rowind + (long)wid * P * m.njrow;
+    int* cnt = (nv + 1) <= SP_LDS_CNT_MAX ? s_cnt : d.sp_cnt + (long)wid * (nv + 1);
+    float* JT_val = d.efc_JT_val + (long)wid * P * m.njrow;
+    unsigned short* idx16 = reinterpret_cast<unsigned short*>(d.sp_idx16 + (long)wid * P * m.njrow);
+    c.JT_adr = JT_adr;
+    c.JT_val = JT_val;
+    c.Jcol16 = idx16;
+    c.JT16 = idx16 + P * m.njrow;
+    c.D = d.efc_D + (long)wid * P;
+    c.fl = d.efc_frictionloss + (long)wid * njmax;
+    c.aref = d.efc_aref + (long)wid * njmax;
+    c.force = d.efc_force + (long)wid * njmax;
+    c.state = d.efc_state + (long)wid * P;
+    c.Jaref = d.sp_row + (long)wid * njmax * 3;
+    c.jv = c.Jaref + njmax;
+    c.Dq = c.Jaref + 2 * njmax;
+    EllCtx ell;
+    if (ELL) {
+      ell.type = d.efc_type + (long)wid * njmax;
+      ell.id = d.efc_id + (long)wid * njmax;
+      ell.con_adr = d.contact_efc_address;
+      ell.con_dim = d.contact_dim;
+      ell.con_fr = d.contact_friction;
+      ell.nmaxpyr = m.nmaxpyramid;
+      ell.iri = MR_W(opt_impratio_invsqrt);
+    }
+    c.ell = ELL ? &ell : nullptr;
+    c.newton = false;
+    c.H = nullptr;
+    // update_constraint's Gauss term reads these; its cost is not used here
+    c.qacc = const_cast<float*>(qacc);
+    c.Ma = Ma;
+    c.qfrc_c = qfrc_c;
+    c.qfrc_s = d.qfrc_smooth + (long)wid * nv;
+    c.qacc_s = d.qacc_smooth + (long)wid * nv;
+    c.cost = MJW_MAXVAL;
+    for (int i = tid(); i <= nv; i += nthr()) cnt[i] = 0;
+    __syncthreads();
+    build_transpose(m, c, qacc, cnt, JT_adr, JT_ind, JT_val, idx16, idx16 + P * m.njrow, sm);
+    __syncthreads();
+    update_constraint<ELL>(c, sm);
+    write_states<ELL>(c);
+  }
+  __syncthreads();
+  const float* bias = d.qfrc_bias + (long)wid * nv;
+  const float* passive = d.qfrc_passive + (long)wid * nv;
+  float* out = d.qfrc_inverse + (long)wid * nv;
+  for (int i = tid(); i < nv; i += nthr()) out[i] = bias[i] + Ma[i] - passive[i] - qfrc_c[i];
+}
+
 // PART 0: qacc from the warmstart, Jaref, and the transposed index of J; PART 1: the CG iterations.
 // Two launches so that the index build (register-resident segment sorts) and the solver loop each
 // get their own register budget.  PART 2 is PART 1 with the per-row line-search state (Jaref, jv)
@@ -3299,79 +3464,7 @@ __global__ void __launch_bounds__(PART == 2 ? SOLVE_LDS_THREADS : BLK, PART == 2
   for (int i = tid(); i <= nv; i += nthr()) cnt[i] = 0;
   for (int i = tid(); i < nv; i += nthr()) qacc[i] = ws ? warm[i] : qacc_s[i];
   __syncthreads();
-  for (int r = tid(); r < c.nefc; r += nthr())
-    for (int k = 0; k < c.Jnnz[r]; k++) atomicAdd(&cnt[c.Jcol[k * P + r]], 1);
-  __syncthreads();
-  int run = 0;
-  for (int c0 = 0; c0 < nv; c0 += nthr()) {
-    const int i = c0 + tid();
-    const int n = i < nv ? cnt[i] : 0;
-    int chunk;
-    const int off = block_scan(n, chunk, sm);
-    if (i < nv) { JT_adr[i] = run + off; cnt[i] = run + off; }
-    run += chunk;
-  }
-  if (tid() == 0) JT_adr[nv] = run;
-  __syncthreads();
-  // fill carries the values (and computes Jaref on the way); the per-column sort of the
-  // (row * njrow + slot) codes then fixes the summation order of J'f whatever the atomics did
-  for (int r = tid(); r < c.nefc; r += nthr()) {
-    float s = 0.0f;
-    for (int k = 0; k < c.Jnnz[r]; k++) {
-      const float v = c.J[k * P + r];
-      const int col = c.Jcol[k * P + r];
-      Jcol16[k * P + r] = (unsigned short)col;
-      const int pos = atomicAdd(&cnt[col], 1);
-      JT_ind[pos] = r * m.njrow + k;
-      JT_val[pos] = v;
-      s += v * qacc[col];
-    }
-    c.Jaref[r] = s - c.aref[r];
-  }
-  __syncthreads();
-  for (int i = tid(); i < nv; i += nthr()) {
-    const int a = JT_adr[i], b = JT_adr[i + 1];
-    if (b - a <= SORTN) {
-      // short segment: loaded at once, odd-even transposition network in registers
-      const int n = b - a;
-      int key[SORTN];
-      float val[SORTN];
-#pragma unroll
-      for (int j = 0; j < SORTN; j++) {
-        key[j] = j < n ? JT_ind[a + j] : 0x7fffffff;
-        val[j] = j < n ? JT_val[a + j] : 0.0f;
-      }
-#pragma unroll
-      for (int r = 0; r < SORTN; r++) {
-#pragma unroll
-        for (int j = r & 1; j + 1 < SORTN; j += 2) {
-          const bool sw = key[j] > key[j + 1];
-          const int k0 = key[j], k1 = key[j + 1];
-          const float v0 = val[j], v1 = val[j + 1];
-          key[j] = sw ? k1 : k0;
-          key[j + 1] = sw ? k0 : k1;
-          val[j] = sw ? v1 : v0;
-          val[j + 1] = sw ? v0 : v1;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < SORTN; j++)
-        if (j < n) {
-          JT16[a + j] = (unsigned short)(key[j] / m.njrow);  // code -> row
-          JT_val[a + j] = val[j];
-        }
-      continue;
-    }
-    for (int p = a + 1; p < b; p++) {
-      const int key = JT_ind[p];
-      const float kv = JT_val[p];
-      int q = p - 1;
-      while (q >= a && JT_ind[q] > key) { JT_ind[q + 1] = JT_ind[q]; JT_val[q + 1] = JT_val[q]; q--; }
-      JT_ind[q + 1] = key;
-      JT_val[q + 1] = kv;
-    }
-    for (int p = a; p < b; p++) JT16[p] = (unsigned short)(JT_ind[p] / m.njrow);  // code -> row
-  }
+  build_transpose(m, c, qacc, cnt, JT_adr, JT_ind, JT_val, Jcol16, JT16, sm);
   return;
   }
   mul_m_trees(m, c.M, qacc, c.Ma);
@@ -3547,6 +3640,18 @@ extern "C" int mjw_prof_read_sparse(unsigned long long* out, int reset) {
   return (int)e;
 }
 #endif
+
+// mjw_inverse on the sparse path: one workgroup per world, the column counters in LDS when they fit
+int sparse_inverse_launch(const mjw_model_t* m, const mjw_data_t* d, hipStream_t s) {
+  const int nw = d->nworld;
+  if (nw <= 0) return 0;
+  const size_t lds = (m->nv + 1) <= sp::SP_LDS_CNT_MAX ? (size_t)(m->nv + 1) * 4 : 0;
+  if (m->opt_cone == CONE_ELLIPTIC)
+    hipLaunchKernelGGL(sp::inverse_kernel<true>, dim3(nw), dim3(sp::BLK), lds, s, *m, *d);
+  else
+    hipLaunchKernelGGL(sp::inverse_kernel<false>, dim3(nw), dim3(sp::BLK), lds, s, *m, *d);
+  return (int)hipGetLastError();
+}
 
 // launcher used by the C entry points (mjw_step.hip) for models with m->is_sparse
 int sparse_launch(int stages, const mjw_model_t* m, const mjw_data_t* d, hipStream_t s) {

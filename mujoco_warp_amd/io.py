@@ -645,6 +645,8 @@ def _data_shapes(m, nworld, njmax, njmax_pad, naconmax):
     efc_JT_val=(njmax_pad * m.njrow * sp,),
     # fixed tendons (smooth.py:3085-3121): lengths, velocities, sparse Jacobian (ten_J_rowadr / _colind)
     ten_length=(m.ntendon,), ten_velocity=(m.ntendon,), ten_J=(m.nJten,),
+    # inverse dynamics output (inverse.py; mjw_inverse)
+    qfrc_inverse=(nv,),
   )
   ints = dict(
     ne=(), nf=(), nl=(), nefc=(), solver_niter=(), moment_rownnz=(nu,), moment_rowadr=(nu,), moment_colind=(m.nJmom,),
@@ -858,6 +860,8 @@ def put_data(mjm, mjd, nworld: int = 1, nconmax: Optional[int] = None, nccdmax: 
     tile("mocap_quat", mjd.mocap_quat, (mjm.nmocap, 4))
   if hasattr(mjd, "qacc"):
     tile("qacc", mjd.qacc, (mjm.nv,))
+  if hasattr(mjd, "qfrc_inverse"):
+    tile("qfrc_inverse", mjd.qfrc_inverse, (mjm.nv,))
   if m.neq:
     eqa = getattr(mjd, "eq_active", mjm.eq_active0)
     d.eq_active[:] = torch.as_tensor(np.asarray(eqa, dtype=np.int32).reshape(m.neq), device=dev)
@@ -888,6 +892,9 @@ def get_data_into(result, mjm, d: types.Data, world_id: int = 0):
       cur[...] = val.reshape(np.shape(cur))
     except AttributeError:
       setattr(result, name, val)
+  if hasattr(result, "qfrc_inverse"):  # only into a destination that has it
+    cur = result.qfrc_inverse
+    cur[...] = d.qfrc_inverse[world_id].detach().cpu().numpy().astype(np.float64).reshape(np.shape(cur))
   result.time = float(d.time[world_id])
   nv = mjm.nv
   nefc = int(d.nefc[world_id])
@@ -964,7 +971,7 @@ def reset_data(m: types.Model, d: types.Data, reset: Optional[torch.Tensor] = No
         getattr(d.contact, f)[hit] = 0
       d.contact.efc_address[hit] = -1
   d.qpos[idx] = _rows(m.qpos0)
-  for name in ("qvel", "act", "ctrl", "qacc_warmstart", "qfrc_applied", "xfrc_applied", "qacc", "act_dot", "sensordata", "energy", "qM"):
+  for name in ("qvel", "act", "ctrl", "qacc_warmstart", "qfrc_applied", "xfrc_applied", "qacc", "act_dot", "sensordata", "energy", "qM", "qfrc_inverse"):
     t = getattr(d, name)
     if t.numel():
       t[idx] = 0

@@ -223,9 +223,10 @@ def passive(m: Model, d: Data):
 
 def rne(m: Model, d: Data, flg_acc: bool = False):
   """qfrc_bias = RNE with zero acceleration (smooth.py:1276-1300, flg_acc = False) from cvel / cdof_dot
-  in d.  flg_acc = True (the inverse-dynamics use, out of this build's scope) is refused."""
+  in d.  flg_acc = True is refused: `inverse` (inverse.py), like the reference's, calls rne with flg_acc = False
+  and adds M qacc through mul_m."""
   if flg_acc:
-    raise NotImplementedError("rne(flg_acc=True) (inverse dynamics) is not part of this build")
+    raise NotImplementedError("rne(flg_acc=True) is not part of this build (inverse() adds M qacc itself)")
   if not _stage("rne", m, d):
     _call("mjw_fwd_velocity", m, d)
 
