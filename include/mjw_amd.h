@@ -19,6 +19,7 @@
  *   mjw_sensor            <- sensor.sensor_pos/_vel/_acc  sensor.py:761,1377,2447
  *   mjw_ctrl_noise        <- benchmark.ctrl_noise         _src/benchmark.py:41-83
  *   mjw_rays              <- ray.rays (no render context) ray.py:1212-1312
+ *   mjw_render            <- render.render (brute force over the geoms, no BVH; no textures, no flex) render.py:515-830
  *   mjw_inverse           <- inverse.inverse's constraint + combine  inverse.py, solver.py init_context(grad=False)
  *
  * Ownership: the caller owns every buffer (device pointers below); the library
@@ -243,6 +244,31 @@ typedef struct mjw_ray_model_t {
   const int32_t* mesh_facenum; /* (nmesh,) */
 } mjw_ray_model_t;
 
+/* A render context (mjw_render): which cameras are rendered at what resolution into which outputs, the tile
+ * table of the launch, the lights' switches and the output buffers.  Every pointer is a device pointer.  Like
+ * mjw_ray_model_t it stays out of mjw_model_t. */
+typedef struct mjw_render_t {
+  uint32_t group_mask;   /* bit g set: geoms of group g are drawn (exact match, groups 0..31) */
+  int32_t use_shadows;   /* shadow rays for lights with castshadow */
+  int32_t nrender;       /* rendered cameras (rows of the camera table) */
+  int32_t ntile;         /* rows of the tile table; 0: nothing to render */
+  int32_t tile_threads;  /* 256: tiles of 16 x 16 pixels; 64: one tile per camera, every camera <= 64 pixels */
+  int32_t pad_;
+  const int32_t* cam_id_map; /* (nrender,) camera id in the model */
+  const int32_t* cam_res;    /* (nrender, 2) width, height */
+  const int32_t* rgb_adr;    /* (nrender,) first pixel of the camera in a row of rgb, -1: output off */
+  const int32_t* depth_adr;  /* (nrender,) likewise for depth */
+  const int32_t* seg_adr;    /* (nrender,) likewise for seg */
+  const int32_t* tile;       /* (ntile, 4) row of the camera table, x0, y0, 0; cameras without an output have none */
+  const int32_t* light_type;       /* (nlight,) 0 spot, 1 directional, 2 point */
+  const int32_t* light_active;     /* (nlight,) */
+  const int32_t* light_castshadow; /* (nlight,) */
+  int32_t* rgb;      /* (nworld, rgb_ld) packed a << 24 | r << 16 | g << 8 | b */
+  float* depth;      /* (nworld, depth_ld) planar depth, 0: background */
+  int32_t* seg;      /* (nworld, seg_ld) geom id, -1: background */
+  int64_t rgb_ld, depth_ld, seg_ld; /* row lengths; the kernel writes no pixel at or past them */
+} mjw_render_t;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -359,6 +385,17 @@ int mjw_primitive_narrowphase(const mjw_model_t* m, const mjw_data_t* d, const i
 int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb, const float* vec,
              int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude, float* dist, int* geomid,
              float* normal, void* stream);
+
+/* Batched camera rendering (render.py `render`): one launch writes, for every world, the segmentation (geom id,
+ * -1 background), planar depth (distance along the optical axis, 0 background) and shaded RGB (packed, background
+ * (25, 25, 51, 255)) images of the context's cameras, from the camera / light / geom frames of the last position stage
+ * (no kinematics run here).  The pixel rays are made in the kernel (render_util.py:67-125) from cam_fovy /
+ * cam_sensorsize / cam_intrinsic, which are read per world (row w % nb).  A geom is drawn iff its group is a bit of
+ * rc->group_mask (no alpha, static or body rule); the nearest hit is found by the geom loop of mjw_rays.  Shading:
+ * hemispheric ambient plus the active lights, with one any-hit shadow pass per castshadow light when use_shadows.
+ * A successful no-op for d->nworld <= 0 or rc->ntile == 0; null arguments give -1, a ray model whose ngeom differs
+ * -4, more workgroups than the grid holds -2. */
+int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, void* stream);
 
 /* Inverse dynamics at the caller's acceleration (inverse.py `inverse`, its constraint and combine steps; ABI 36):
  * with the position and velocity stages of the current state in `d` (qM, qfrc_bias, qfrc_passive and the constraint

@@ -6,11 +6,14 @@
 // it to the world frame (rot_to_world).  lv is not normalised: x is in units of |lv|.  They keep no state and
 // read nothing but their arguments, so a sensor kernel can call them per lane as the ray kernel does.
 //
+// The geom loop at the end of the file (staging in LDS, culling, nearest / any hit) is what rays_kernel and
+// render_kernel share.
+//
 // The touch sensor's distance-only routines (mjw_sensor.h ray_quad / ray_geom_local) are separate and
 // unchanged; these live in their own namespace.
 #pragma once
 
-#include "mjw_math.h"
+#include "mjw_common.h"
 
 namespace mjw {
 namespace ray {
@@ -329,6 +332,179 @@ __device__ __forceinline__ float ray_hfield(const float* hsize, int nrow, int nc
     }
   }
   return x;
+}
+
+// ---- the geom loop shared by rays_kernel (mjw_ray.hip) and render_kernel (mjw_render.hip) -------------------
+//
+// One workgroup serves one world; the geoms are staged in LDS in chunks of RAY_CHUNK records and every lane
+// walks the staged chunk with its own ray, so a geom's type, frame, size and mesh faces are wave-uniform.
+
+constexpr int RAY_CHUNK = 128;  // geoms staged in LDS at a time
+// words of a staged record: pos 3, mat 9, size 3, aabb 6 (centre, half extents; geom frame), bounding ball
+// (world-frame centre 3, squared radius 1), then four ints: type, data id, body id, eliminated
+enum : int { R_POS = 0, R_MAT = 3, R_SIZE = 12, R_AABB = 15, R_BALL = 21, R_TYPE = 25, R_DATA = 26, R_BODY = 27, R_ELIM = 28 };
+constexpr int RECW = 29;
+
+// the geom arrays the loop reads (a small block instead of mjw_model_t / mjw_data_t by value)
+struct GeomArgs {
+  int ngeom, nmat, nmeshface, nmesh, nhfield, nmeshvert, nhfielddata;
+  // which geoms are left out.  draw_rule 0 (rays, ray.py:52-102 without the per-ray body exclusion): alpha 0,
+  // static bodies when !flg_static, and group_mask >= 0 without bit clamp(geom_group, 0, 5).  draw_rule 1
+  // (render, render.py:89-253): exactly the geoms whose group is no bit of draw_groups; no alpha or static rule.
+  int flg_static, group_mask, draw_rule;
+  unsigned draw_groups;
+  int size_nb, aabb_nb, rgba_nb, matrgba_nb, vert_nb, hsize_nb, hdata_nb;
+  const float *geom_xpos, *geom_xmat;
+  const float *geom_size, *geom_aabb, *geom_rgba, *mat_rgba, *mesh_vert, *hfield_size, *hfield_data;
+  const int *geom_type, *geom_bodyid, *geom_dataid, *geom_group, *geom_matid, *body_weldid;
+  const int *mesh_vertadr, *mesh_face, *mesh_faceadr, *mesh_facenum, *hfield_nrow, *hfield_ncol, *hfield_adr;
+};
+
+// host: the argument checks of the geom arrays (the entry point's name goes into the message) ...
+inline int check_geom_args(const char* who, const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm) {
+  const std::string w(who);
+  if (rm->ngeom != m->ngeom) return set_last_error(-4, (w + ": ray model ngeom differs from the model's").c_str());
+  if (m->ngeom > 0 && (!rm->geom_group || !rm->geom_matid || !rm->geom_rgba || rm->geom_rgba_nb < 1 || !d->geom_xpos || !d->geom_xmat))
+    return set_last_error(-1, (w + ": null geom array").c_str());
+  if (rm->nmat > 0 && (!rm->mat_rgba || rm->mat_rgba_nb < 1)) return set_last_error(-1, (w + ": null mat_rgba").c_str());
+  if (rm->nmeshface > 0 && (!rm->mesh_face || !rm->mesh_faceadr || !rm->mesh_facenum)) return set_last_error(-1, (w + ": null mesh face array").c_str());
+  return 0;
+}
+
+// ... and the block filled from the model, the data and the ray model (the draw rule's fields are the caller's)
+inline void fill_geom_args(GeomArgs& a, const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm) {
+  a.ngeom = m->ngeom;
+  a.nmat = rm->nmat; a.nmeshface = rm->nmeshface; a.nmesh = rm->nmeshface > 0 ? m->nmesh : 0; a.nhfield = m->nhfield;
+  a.geom_xpos = d->geom_xpos; a.geom_xmat = d->geom_xmat;
+  a.geom_size = m->geom_size; a.size_nb = m->geom_size_nb;
+  a.geom_aabb = m->geom_aabb; a.aabb_nb = m->geom_aabb_nb;
+  a.geom_rgba = rm->geom_rgba; a.rgba_nb = rm->geom_rgba_nb;
+  a.mat_rgba = rm->mat_rgba; a.matrgba_nb = rm->mat_rgba_nb;
+  a.mesh_vert = m->mesh_vert; a.vert_nb = m->mesh_vert_nb; a.nmeshvert = m->nmeshvert;
+  a.hfield_size = m->hfield_size; a.hsize_nb = m->hfield_size_nb;
+  a.hfield_data = m->hfield_data; a.hdata_nb = m->hfield_data_nb; a.nhfielddata = m->nhfielddata;
+  a.geom_type = m->geom_type; a.geom_bodyid = m->geom_bodyid; a.geom_dataid = m->geom_dataid;
+  a.geom_group = rm->geom_group; a.geom_matid = rm->geom_matid; a.body_weldid = m->body_weldid;
+  a.mesh_vertadr = m->mesh_vertadr; a.mesh_face = rm->mesh_face; a.mesh_faceadr = rm->mesh_faceadr; a.mesh_facenum = rm->mesh_facenum;
+  a.hfield_nrow = m->hfield_nrow; a.hfield_ncol = m->hfield_ncol; a.hfield_adr = m->hfield_adr;
+}
+
+__device__ __forceinline__ const float* row(const float* p, int nb, long cnt, int w) { return nb <= 1 ? p : p + (long)(w % nb) * cnt; }
+__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+// stages geoms g0 .. g0 + n of world wid (the caller puts the barriers around it)
+template <int NT>
+__device__ __forceinline__ void stage_chunk(const GeomArgs& a, int wid, int g0, int n, float* recs) {
+  const float* size_w = row(a.geom_size, a.size_nb, (long)a.ngeom * 3, wid);
+  const float* aabb_w = row(a.geom_aabb, a.aabb_nb, (long)a.ngeom * 6, wid);
+  const float* rgba_w = row(a.geom_rgba, a.rgba_nb, (long)a.ngeom * 4, wid);
+  const float* matrgba_w = row(a.mat_rgba, a.matrgba_nb, (long)a.nmat * 4, wid);
+  const float* xpos_w = a.geom_xpos + (long)wid * a.ngeom * 3;
+  const float* xmat_w = a.geom_xmat + (long)wid * a.ngeom * 9;
+  for (int k = threadIdx.x; k < n; k += NT) {
+    const int g = g0 + k;
+    float* rec = recs + k * RECW;
+    for (int i = 0; i < 3; i++) rec[R_POS + i] = xpos_w[3 * g + i];
+    for (int i = 0; i < 9; i++) rec[R_MAT + i] = xmat_w[9 * g + i];
+    for (int i = 0; i < 3; i++) rec[R_SIZE + i] = size_w[3 * g + i];
+    for (int i = 0; i < 6; i++) rec[R_AABB + i] = aabb_w[6 * g + i];
+    // bounding ball: centre = pos + mat aabb_centre, radius = |half extents| (a little generous, so that
+    // rounding never culls a ray the exact routine would accept)
+    const float* c = rec + R_AABB;
+    for (int i = 0; i < 3; i++)
+      rec[R_BALL + i] = rec[R_POS + i] + rec[R_MAT + 3 * i] * c[0] + rec[R_MAT + 3 * i + 1] * c[1] + rec[R_MAT + 3 * i + 2] * c[2];
+    rec[R_BALL + 3] = (c[3] * c[3] + c[4] * c[4] + c[5] * c[5]) * 1.002f + 1e-12f;
+    const int body = a.geom_bodyid[g], matid = a.geom_matid[g];
+    bool elim;
+    if (a.draw_rule == 0) {
+      elim = matid < 0 ? rgba_w[4 * g + 3] == 0.0f : (matid < a.nmat && matrgba_w[4 * matid + 3] == 0.0f);
+      if (!a.flg_static && a.body_weldid[body] == 0) elim = true;
+      if (a.group_mask >= 0 && !((a.group_mask >> min(5, max(0, a.geom_group[g]))) & 1)) elim = true;
+    } else {
+      const int grp = a.geom_group[g];
+      elim = grp < 0 || grp > 31 || !((a.draw_groups >> grp) & 1u);
+    }
+    int* ri = reinterpret_cast<int*>(rec);
+    ri[R_TYPE] = a.geom_type[g];
+    ri[R_DATA] = a.geom_dataid[g];
+    ri[R_BODY] = body;
+    ri[R_ELIM] = elim ? 1 : 0;
+  }
+}
+
+// Every lane's ray (pnt, vec; world frame) against the n staged geoms g0 ..: a hit nearer than `best` (strict
+// `<`, so equal distances stay with the lowest geom id) replaces best / bid / bn (world-frame normal).  Lanes
+// with !active, and geoms of body excl, are left alone.  ANYHIT: a lane that has a hit (bid >= 0) stops looking,
+// so with best preset to a distance limit the result says only whether anything lies nearer than the limit.
+template <bool ANYHIT>
+__device__ __forceinline__ void trace_chunk(const GeomArgs& a, int wid, const float* recs, int g0, int n, bool active, int excl,
+                                            const float* pnt, const float* vec, float& best, int& bid, float* bn) {
+  for (int k = 0; k < n; k++) {
+    const float* rec = recs + k * RECW;
+    const int* ri = reinterpret_cast<const int*>(rec);
+    if (uni(ri[R_ELIM])) continue;  // eliminated for every ray of the workgroup
+    const int type = uni(ri[R_TYPE]);
+    bool cand = active && ri[R_BODY] != excl;
+    if (ANYHIT) cand = cand && bid < 0;
+    if (type != RG_PLANE) cand = cand && ball_test(rec + R_BALL, rec[R_BALL + 3], pnt, vec);
+    if (!__any(cand)) continue;  // no ray of this wave can hit the geom
+
+    float lp[3], lv[3], nl[3] = {0.0f, 0.0f, 0.0f};
+    ray_map(rec + R_POS, rec + R_MAT, pnt, vec, lp, lv);
+    float x = -1.0f;
+    if (type == RG_MESH) {
+      // ray.py:622-697 with the bounding box of geom_aabb (centre and half extents in the geom frame)
+      const float lpc[3] = {lp[0] - rec[R_AABB], lp[1] - rec[R_AABB + 1], lp[2] - rec[R_AABB + 2]};
+      cand = cand && box_test(rec + R_AABB + 3, lpc, lv);
+      if (!__any(cand)) continue;
+      const int mesh = uni(ri[R_DATA]);
+      if (mesh < 0 || mesh >= a.nmesh) continue;
+      float b0[3], b1[3];
+      ray_basis(lv, b0, b1);
+      // the face loop is wave-uniform: indices and vertices are read through uniform addresses
+      const float* vert = row(a.mesh_vert, a.vert_nb, (long)a.nmeshvert * 3, wid) + 3 * (long)a.mesh_vertadr[mesh];
+      const int f0 = a.mesh_faceadr[mesh], f1 = min(f0 + a.mesh_facenum[mesh], a.nmeshface);
+      for (int f = f0; f < f1; f++) {
+        const int* idx = a.mesh_face + 3 * (long)f;
+        float n[3];
+        const float sol = ray_triangle(vert + 3 * idx[0], vert + 3 * idx[1], vert + 3 * idx[2], lp, lv, b0, b1, n);
+        if (sol >= 0.0f && (x < 0.0f || sol < x)) {
+          x = sol;
+          nl[0] = n[0]; nl[1] = n[1]; nl[2] = n[2];
+        }
+      }
+    } else if (type == RG_HFIELD) {
+      const int hid = uni(ri[R_DATA]);
+      if (hid < 0 || hid >= a.nhfield) continue;
+      const float* hsize = row(a.hfield_size, a.hsize_nb, (long)a.nhfield * 4, wid) + 4 * hid;
+      const float* data = row(a.hfield_data, a.hdata_nb, (long)a.nhfielddata, wid) + a.hfield_adr[hid];
+      if (cand) x = ray_hfield(hsize, a.hfield_nrow[hid], a.hfield_ncol[hid], data, lp, lv, nl);
+    } else {
+      x = ray_geom(type, rec + R_SIZE, lp, lv, nl);
+    }
+    if (cand && x >= 0.0f && x < best) {
+      best = x;
+      bid = g0 + k;
+      rot_to_world(rec + R_MAT, nl, bn);
+    }
+  }
+}
+
+// The whole loop: every chunk of world wid staged in `recs` (RAY_CHUNK * RECW floats of LDS) and traced.  Every
+// thread of the workgroup must call it (it holds barriers); a wave without an active lane skips the tracing.
+// staged: the model fits one chunk and an earlier call of this workgroup left it in `recs`.
+template <int NT, bool ANYHIT>
+__device__ __forceinline__ void geom_loop(const GeomArgs& a, int wid, float* recs, bool staged, bool active, int excl, const float* pnt,
+                                          const float* vec, float& best, int& bid, float* bn) {
+  for (int g0 = 0; g0 < a.ngeom; g0 += RAY_CHUNK) {
+    const int n = min(RAY_CHUNK, a.ngeom - g0);
+    if (!staged) {
+      __syncthreads();  // the previous chunk is consumed
+      stage_chunk<NT>(a, wid, g0, n, recs);
+      __syncthreads();
+    }
+    if (__any(active)) trace_chunk<ANYHIT>(a, wid, recs, g0, n, active, excl, pnt, vec, best, bid, bn);
+  }
 }
 
 }  // namespace ray

@@ -1,0 +1,221 @@
+// mjw_render.hip -- batched camera rendering: segmentation, planar depth and shaded RGB images of a model's
+// cameras (mjw_render; mujoco_warp/_src/render.py `render`, render_util.py:67-125 `compute_ray`).
+//
+// Mapping: one workgroup serves one world, one rendered camera and a 16 x 16 tile of its pixels; each of the
+// four waves owns an 8 x 8 block of the tile, so the rays of a wave stay close together and the wave-wide
+// ball / box culling of the shared geom loop (geom_loop, mjw_ray.h) skips most geoms.  When every rendered
+// camera has at most 64 pixels the workgroup is one wave and covers a whole image, pixel = lane.  A device
+// table per render context maps the tile index to the camera and the tile's origin.  The rays are made in the
+// kernel from the camera frames the last position stage left and the per-world camera parameters; they never
+// exist in memory.  The kernel writes every pixel of every enabled output, background included.
+//
+// Shading (render.py:680-769, 410-512): hemispheric ambient plus the active lights; with shadows, one any-hit
+// pass of the geom loop per shadow-casting light from the hit point towards the light, traced only by the
+// waves in which some lane faces the light.  Lights are read through wave-uniform addresses.
+#include "mjw_common.h"
+#include "mjw_ray.h"
+
+namespace mjw {
+namespace ray {
+
+struct RenderArgs {
+  GeomArgs g;
+  int nworld, ntile, nrender, ncam, nlight, use_shadows, fovy_nb, sensor_nb, intr_nb, pad_;
+  long rgb_ld, depth_ld, seg_ld;
+  const float *cam_xpos, *cam_xmat, *light_xpos, *light_xdir, *cam_fovy, *cam_sensorsize, *cam_intrinsic;
+  const int *cam_id_map, *cam_res, *rgb_adr, *depth_adr, *seg_adr, *tile;
+  const int *light_type, *light_active, *light_castshadow;
+  int* rgb;
+  float* depth;
+  int* seg;
+};
+
+constexpr unsigned BACKGROUND = 255u << 24 | 25u << 16 | 25u << 8 | 51u;  // (0.1, 0.1, 0.2, 1) * 255, truncated
+
+// render_util.py:67-125 at znear = 1 (it cancels in the normalisation): the direction of pixel (px, py) of a
+// W x H image in the camera frame
+__device__ __forceinline__ void pixel_ray(float fovy, const float* sensorsize, const float* intrinsic, int W, int H, int px, int py,
+                                          float* local) {
+  const float aspect = (float)W / (float)H;
+  float left, right, top, bottom;
+  float sensor_h = sensorsize[1];
+  if (sensor_h != 0.0f) {
+    const float fx = intrinsic[0], fy = intrinsic[1], cx = intrinsic[2], cy = intrinsic[3];
+    float sensor_w = sensorsize[0];
+    const float sensor_aspect = sensor_w / sensor_h;
+    if (aspect > sensor_aspect)
+      sensor_h = sensor_w / aspect;
+    else if (aspect < sensor_aspect)
+      sensor_w = sensor_h * aspect;
+    const float ifx = 1.0f / fx, ify = 1.0f / fy;
+    left = -ifx * (sensor_w * 0.5f - cx);
+    right = ifx * (sensor_w * 0.5f + cx);
+    top = ify * (sensor_h * 0.5f - cy);
+    bottom = -ify * (sensor_h * 0.5f + cy);
+  } else {
+    const float half_h = tanf(0.5f * fovy * 0.017453292519943295f);
+    const float half_w = half_h * aspect;
+    left = -half_w; right = half_w; top = half_h; bottom = -half_h;
+  }
+  const float u = ((float)px + 0.5f) / (float)W, v = ((float)py + 0.5f) / (float)H;
+  local[0] = left + (right - left) * u;
+  local[1] = top + (bottom - top) * v;
+  local[2] = -1.0f;
+  normalize3(local);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
+  __shared__ float recs[RAY_CHUNK * RECW];
+  const int tid = threadIdx.x;
+  const int wid = blockIdx.x / a.ntile, t = blockIdx.x - wid * a.ntile;
+  const int ci = a.tile[4 * t], x0 = a.tile[4 * t + 1], y0 = a.tile[4 * t + 2];
+  if (ci < 0 || ci >= a.nrender || x0 < 0 || y0 < 0) return;  // (uniform over the workgroup)
+  const int W = a.cam_res[2 * ci], H = a.cam_res[2 * ci + 1], cam = a.cam_id_map[ci];
+  if (W < 1 || H < 1 || cam < 0 || cam >= a.ncam) return;
+  int lx, ly;
+  if (NT == 64) {  // the whole image of at most 64 pixels
+    lx = tid % W;
+    ly = tid / W;
+  } else {  // wave w owns the 8 x 8 block (w & 1, w >> 1) of the tile
+    const int wave = tid >> 6, lane = tid & 63;
+    lx = (wave & 1) * 8 + (lane & 7);
+    ly = (wave >> 1) * 8 + (lane >> 3);
+  }
+  const int px = x0 + lx, py = y0 + ly;
+  const bool active = px < W && py < H;
+  const int pxc = min(px, W - 1), pyc = min(py, H - 1);  // idle lanes follow a valid pixel and write nothing
+
+  // the ray
+  const float fovy = row(a.cam_fovy, a.fovy_nb, a.ncam, wid)[cam];
+  const float* ss = row(a.cam_sensorsize, a.sensor_nb, (long)a.ncam * 2, wid) + 2 * cam;
+  const float* in = row(a.cam_intrinsic, a.intr_nb, (long)a.ncam * 4, wid) + 4 * cam;
+  float local[3], vec[3];
+  pixel_ray(fovy, ss, in, W, H, pxc, pyc, local);
+  const float* cp = a.cam_xpos + ((long)wid * a.ncam + cam) * 3;
+  const float* cm = a.cam_xmat + ((long)wid * a.ncam + cam) * 9;
+  const float pnt[3] = {cp[0], cp[1], cp[2]};
+  rot_to_world(cm, local, vec);
+
+  float best = MJW_MAXVAL, bn[3] = {0.0f, 0.0f, 0.0f};
+  int bid = -1;
+  geom_loop<NT, false>(a.g, wid, recs, false, active, -1, pnt, vec, best, bid, bn);
+  const bool hit = bid >= 0;
+
+  const long pix = (long)py * W + px;
+  const int sadr = a.seg_adr[ci], dadr = a.depth_adr[ci], cadr = a.rgb_adr[ci];
+  if (active && sadr >= 0 && sadr + pix < a.seg_ld) a.seg[(long)wid * a.seg_ld + sadr + pix] = bid;
+  if (active && dadr >= 0 && dadr + pix < a.depth_ld) a.depth[(long)wid * a.depth_ld + dadr + pix] = hit ? best * -local[2] : 0.0f;
+  if (cadr < 0) return;  // (uniform over the workgroup)
+
+  // shading: every thread goes through the light loop (the shadow pass holds barriers), a lane without a hit
+  // takes no part in it
+  const int gid = hit ? bid : 0;
+  const int matid = a.g.ngeom > 0 ? a.g.geom_matid[gid] : -1;
+  const float* col = (matid >= 0 && matid < a.g.nmat) ? row(a.g.mat_rgba, a.g.matrgba_nb, (long)a.g.nmat * 4, wid) + 4 * matid
+                                                       : row(a.g.geom_rgba, a.g.rgba_nb, (long)a.g.ngeom * 4, wid) + 4 * gid;
+  float base[3] = {0.0f, 0.0f, 0.0f};
+  if (hit)
+    for (int i = 0; i < 3; i++) base[i] = col[i];
+  const float hp[3] = {pnt[0] + vec[0] * best, pnt[1] + vec[1] * best, pnt[2] + vec[2] * best};
+  float n[3] = {bn[0], bn[1], bn[2]};
+  if (!(dot3(n, n) > 0.0f)) { n[0] = 0.0f; n[1] = 0.0f; n[2] = 1.0f; }
+  normalize3(n);
+  const float h = 0.5f * (n[2] + 1.0f);
+  float res[3] = {0.5f * base[0] * (0.4f * h + 0.1f * (1.0f - h)), 0.5f * base[1] * (0.4f * h + 0.1f * (1.0f - h)),
+                  0.5f * base[2] * (0.45f * h + 0.12f * (1.0f - h))};
+
+  for (int l = 0; l < a.nlight; l++) {
+    if (!a.light_active[l]) continue;
+    const int type = a.light_type[l];
+    const float* lpos = a.light_xpos + ((long)wid * a.nlight + l) * 3;
+    const float* ldir = a.light_xdir + ((long)wid * a.nlight + l) * 3;
+    float L[3], r = MJW_MAXVAL, att = 1.0f;
+    if (type == 1) {  // directional
+      L[0] = -ldir[0]; L[1] = -ldir[1]; L[2] = -ldir[2];
+      normalize3(L);
+    } else {
+      L[0] = lpos[0] - hp[0]; L[1] = lpos[1] - hp[1]; L[2] = lpos[2] - hp[2];
+      r = sqrtf(dot3(L, L));
+      const float inv = r > 0.0f ? 1.0f / r : 0.0f;
+      L[0] *= inv; L[1] *= inv; L[2] *= inv;
+      att = 1.0f / (1.0f + 0.02f * r * r);
+      if (type == 0) {  // spot
+        float sd[3] = {ldir[0], ldir[1], ldir[2]};
+        normalize3(sd);
+        const float cs = -dot3(L, sd);
+        att *= fminf(1.0f, fmaxf(0.0f, (cs - 0.85f) / (0.95f - 0.85f)));
+      }
+    }
+    const float ndotl = hit ? fmaxf(0.0f, dot3(bn, L)) : 0.0f;
+    float visible = 1.0f;
+    if (a.use_shadows && a.light_castshadow[l]) {
+      const float so[3] = {hp[0] + bn[0] * 1e-4f, hp[1] + bn[1] * 1e-4f, hp[2] + bn[2] * 1e-4f};
+      float sbest = type == 1 ? 1e8f : r - 1e-3f, sn[3];
+      int sid = -1;
+      geom_loop<NT, true>(a.g, wid, recs, a.g.ngeom <= RAY_CHUNK, active && ndotl > 0.0f, -1, so, L, sbest, sid, sn);
+      if (sid >= 0) visible = 0.3f;
+    }
+    const float c = ndotl * att * visible;
+    for (int i = 0; i < 3; i++) res[i] += base[i] * c;
+  }
+
+  if (active && cadr + pix < a.rgb_ld) {
+    unsigned packed = BACKGROUND;
+    if (hit) {
+      unsigned byte[3];
+      for (int i = 0; i < 3; i++) byte[i] = (unsigned)(int)(fminf(1.0f, fmaxf(0.0f, res[i])) * 255.0f);
+      packed = 255u << 24 | byte[0] << 16 | byte[1] << 8 | byte[2];
+    }
+    a.rgb[(long)wid * a.rgb_ld + cadr + pix] = (int)packed;
+  }
+}
+
+}  // namespace ray
+}  // namespace mjw
+
+extern "C" int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, void* stream) {
+  using namespace mjw::ray;
+  if (!m || !d || !rm || !rc) return mjw::set_last_error(-1, "mjw_render: null model / data / ray model / render context");
+  if (rc->ntile < 0 || rc->nrender < 0) return mjw::set_last_error(-4, "mjw_render: ntile / nrender < 0");
+  if (rc->ntile == 0 || d->nworld <= 0) return 0;
+  if (rc->tile_threads != 64 && rc->tile_threads != 256) return mjw::set_last_error(-4, "mjw_render: tile_threads must be 64 or 256");
+  if (!rc->cam_id_map || !rc->cam_res || !rc->rgb_adr || !rc->depth_adr || !rc->seg_adr || !rc->tile)
+    return mjw::set_last_error(-1, "mjw_render: null camera / tile table");
+  if ((rc->rgb_ld > 0 && !rc->rgb) || (rc->depth_ld > 0 && !rc->depth) || (rc->seg_ld > 0 && !rc->seg) || rc->rgb_ld < 0 || rc->depth_ld < 0 ||
+      rc->seg_ld < 0)
+    return mjw::set_last_error(-1, "mjw_render: null output array");
+  if (m->ncam <= 0 || !d->cam_xpos || !d->cam_xmat || !m->cam_fovy || !m->cam_sensorsize || !m->cam_intrinsic)
+    return mjw::set_last_error(-1, "mjw_render: null camera array");
+  if (m->nlight > 0 && (!d->light_xpos || !d->light_xdir || !rc->light_type || !rc->light_active || !rc->light_castshadow))
+    return mjw::set_last_error(-1, "mjw_render: null light array");
+  if (int e = check_geom_args("mjw_render", m, d, rm)) return e;
+
+  RenderArgs a;
+  memset(&a, 0, sizeof(a));
+  fill_geom_args(a.g, m, d, rm);
+  a.g.draw_rule = 1;
+  a.g.draw_groups = rc->group_mask;
+  a.nworld = d->nworld; a.ntile = rc->ntile; a.nrender = rc->nrender; a.ncam = m->ncam; a.nlight = m->nlight;
+  a.use_shadows = rc->use_shadows != 0;
+  a.cam_xpos = d->cam_xpos; a.cam_xmat = d->cam_xmat; a.light_xpos = d->light_xpos; a.light_xdir = d->light_xdir;
+  a.cam_fovy = m->cam_fovy; a.fovy_nb = m->cam_fovy_nb;
+  a.cam_sensorsize = m->cam_sensorsize; a.sensor_nb = m->cam_sensorsize_nb;
+  a.cam_intrinsic = m->cam_intrinsic; a.intr_nb = m->cam_intrinsic_nb;
+  a.cam_id_map = rc->cam_id_map; a.cam_res = rc->cam_res; a.rgb_adr = rc->rgb_adr; a.depth_adr = rc->depth_adr; a.seg_adr = rc->seg_adr;
+  a.tile = rc->tile;
+  a.light_type = rc->light_type; a.light_active = rc->light_active; a.light_castshadow = rc->light_castshadow;
+  a.rgb = rc->rgb; a.depth = rc->depth; a.seg = rc->seg;
+  a.rgb_ld = rc->rgb_ld; a.depth_ld = rc->depth_ld; a.seg_ld = rc->seg_ld;
+
+  hipStream_t s = (hipStream_t)stream;
+  const long nblock = (long)a.nworld * a.ntile;
+  if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, "mjw_render: nworld x tiles exceeds the grid limit");
+  if (rc->tile_threads == 64)
+    hipLaunchKernelGGL(render_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a);
+  else
+    hipLaunchKernelGGL(render_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return mjw::set_last_error((int)e, hipGetErrorString(e));
+  return 0;
+}

@@ -453,6 +453,11 @@ def put_model(mjm, device=None) -> types.Model:
   m.mesh_face = _i32(np.asarray(getattr(mjm, "mesh_face", np.zeros((0, 3)))).reshape(m.nmeshface, 3), dev)
   m.mesh_faceadr = _i32(np.asarray(getattr(mjm, "mesh_faceadr", np.zeros(0))), dev)
   m.mesh_facenum = _i32(np.asarray(getattr(mjm, "mesh_facenum", np.zeros(0))), dev)
+  # rendering (render.py): each light's kind and switches (a host model without them: active spot lights that cast shadows)
+  nl = int(mjm.nlight)
+  m.light_type = _i32(np.asarray(getattr(mjm, "light_type", np.zeros(nl))).reshape(-1)[:nl], dev)
+  m.light_active = _i32(np.asarray(getattr(mjm, "light_active", np.ones(nl))).reshape(-1)[:nl].astype(np.int32), dev)
+  m.light_castshadow = _i32(np.asarray(getattr(mjm, "light_castshadow", np.ones(nl))).reshape(-1)[:nl].astype(np.int32), dev)
   m._mjm_sizes = dict(nq=mjm.nq, nv=nv)
   return m
 

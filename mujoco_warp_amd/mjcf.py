@@ -93,6 +93,7 @@ _GEOM_TYPES = {
   "sdf": GeomType.SDF,
 }
 _JOINT_TYPES = {"free": JointType.FREE, "ball": JointType.BALL, "slide": JointType.SLIDE, "hinge": JointType.HINGE}
+_LIGHT_TYPES = {"spot": 0, "directional": 1, "point": 2}
 _CAMLIGHT_MODES = {
   "fixed": CamLightType.FIXED,
   "track": CamLightType.TRACK,
@@ -1549,6 +1550,12 @@ class _Compiler:
       for la in b.lights:
         d = np.array(_floats(la.get("dir", "0 0 -1"), 3))
         d = d / max(np.linalg.norm(d), MJ_MINVAL)
+        # mjtLightType: spot 0 (the default), directional 1, point 2; the older directional="true" means type 1
+        ltype = la.get("type")
+        if ltype is None:
+          ltype = "directional" if la.get("directional", "false") == "true" else "spot"
+        if ltype not in _LIGHT_TYPES:
+          raise NotImplementedError(f"light type '{ltype}' is not supported (spot, directional and point only)")
         lrows.append(
           dict(
             bodyid=i,
@@ -1557,6 +1564,9 @@ class _Compiler:
             target=la.get("target"),
             pos=_floats(la.get("pos", "0 0 0"), 3),
             dir=d,
+            type=_LIGHT_TYPES[ltype],
+            active=la.get("active", "true") == "true",
+            castshadow=la.get("castshadow", "true") == "true",
           )
         )
     name2body = {b.name: i for i, b in enumerate(self.bodies)}
@@ -1585,6 +1595,10 @@ class _Compiler:
     m.light_targetbodyid = np.array([name2body[r["target"]] if r["target"] else -1 for r in lrows], dtype=np.int32)
     m.light_pos = np.array([r["pos"] for r in lrows]).reshape(-1, 3)
     m.light_dir = np.array([r["dir"] for r in lrows]).reshape(-1, 3)
+    # what the renderer reads (render.py:410-512)
+    m.light_type = np.array([r["type"] for r in lrows], dtype=np.int32)
+    m.light_active = np.array([r["active"] for r in lrows], dtype=bool)
+    m.light_castshadow = np.array([r["castshadow"] for r in lrows], dtype=bool)
 
   def _build_tendons(self, root):
     """<tendon><fixed>: fixed (joint) tendons, length = sum coef * qpos (smooth.py:3085-3121); <tendon><spatial>:

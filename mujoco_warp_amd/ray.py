@@ -2,9 +2,9 @@
 
 One HIP launch (`mjw_rays`, csrc/mjw_ray.hip) on the Data's stream: for every world and ray the nearest geom
 along `pnt + x vec`, x >= 0, at the frames `d.geom_xpos` / `d.geom_xmat` the last position stage left (no
-kinematics run here, so it serves dense and sparse models alike).  There is no BVH or render context in this
-build: `rc` other than None is refused, and flex elements are not hit (as on the reference's path without
-`rc`).  Meshes are brute force over their triangles.
+kinematics run here, so it serves dense and sparse models alike).  There is no BVH in this build, so a render
+context (render.py) accelerates nothing here: `rc` other than None is refused, and flex elements are not hit
+(as on the reference's path without `rc`).  Meshes are brute force over their triangles.
 """
 
 from __future__ import annotations

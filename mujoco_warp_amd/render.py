@@ -1,0 +1,245 @@
+"""Batched camera rendering: segmentation, depth and shaded RGB images of a model's cameras
+(mujoco_warp/_src/render.py `render`, io.py `create_render_context`, render_util.py readers).
+
+One HIP launch (`mjw_render`, csrc/mjw_render.hip) on the Data's stream per `render` call: a workgroup per
+world, camera and 16 x 16 pixel tile makes the pixel rays from `d.cam_xpos` / `d.cam_xmat` and the per-world
+camera parameters, finds the nearest geom with the geom loop `rays` uses, and writes every pixel of every
+enabled output.  No kinematics run here: the frames are those the last position stage left.  This build has no
+BVH (`refit_bvh` does nothing), no textures, no flex rendering and no orthographic cameras.
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .types import Data, Model, RenderContext
+
+TILE = 16  # pixels per side of a workgroup's tile (csrc/mjw_render.hip)
+_CAMOUT_RGB, _CAMOUT_DEPTH, _CAMOUT_SEG = 1, 2, 16  # mjtCamOutBit
+
+
+def _flags(given, ncam, mjm, active, bit, default):
+  if given is None:
+    out = getattr(mjm, "cam_output", None)
+    return [bool(int(out[i]) & bit) for i in active] if out is not None else [default] * ncam
+  if isinstance(given, (bool, np.bool_)):
+    return [bool(given)] * ncam
+  return [bool(x) for x in given]
+
+
+def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, render_depth=None, render_seg=None, use_textures: bool = True,
+                          use_shadows: bool = False, enabled_geom_groups: Sequence[int] = [0, 1, 2], cam_active: Optional[Sequence[bool]] = None,
+                          flex_render_smooth: bool = True, use_precomputed_rays: bool = True, device=None) -> RenderContext:
+  """Creates a render context on the device (io.py:2649-2904).
+
+  cam_res: one (width, height) tuple for every active camera, a list with one per active camera, or None for
+  `mjm.cam_resolution`.  render_rgb / render_depth / render_seg: a bool, a list with one bool per active camera,
+  or None for the model's `cam_output` bits where the host model carries them, else RGB only.  A geom is drawn
+  iff its group is one of enabled_geom_groups (each in 0..31).  cam_active: one bool per model camera (None: all).
+  use_shadows: lights with castshadow throw shadows.
+
+  Accepted and ignored: `use_textures` (the MJCF compiler keeps no textures, colours are mat_rgba / geom_rgba),
+  `flex_render_smooth` (no flex rendering) and `use_precomputed_rays` (the rays are always made in the kernel, so
+  per-world cam_fovy / cam_intrinsic work).  A model with flexes raises NotImplementedError: its flex elements
+  would be silently invisible."""
+  from .io import _device
+
+  if int(getattr(mjm, "nflex", 0)) > 0:
+    raise NotImplementedError("create_render_context: flex rendering is not part of this build (the model has flexes)")
+  dev = _device(device)
+  nworld = int(nworld)
+  if nworld < 1:
+    raise ValueError(f"create_render_context: nworld must be positive, got {nworld}")
+  ncam_model = int(mjm.ncam)
+  if cam_active is not None:
+    assert len(cam_active) == ncam_model, f"cam_active must have length {ncam_model} (got {len(cam_active)})"
+    active = [i for i, on in enumerate(cam_active) if on]
+  else:
+    active = list(range(ncam_model))
+  ncam = len(active)
+
+  if cam_res is not None:
+    if isinstance(cam_res, tuple):
+      cam_res = [cam_res] * ncam
+    assert len(cam_res) == ncam, f"Camera resolutions must be provided for all active cameras (got {len(cam_res)}, expected {ncam})"
+    res = np.asarray(cam_res, dtype=np.int64).reshape(ncam, 2)
+  else:
+    res = np.asarray(mjm.cam_resolution, dtype=np.int64).reshape(ncam_model, 2)[active]
+  if ncam and res.min() < 1:
+    raise ValueError(f"create_render_context: camera resolutions must be positive, got {res.tolist()}")
+
+  rgb = _flags(render_rgb, ncam, mjm, active, _CAMOUT_RGB, True)
+  depth = _flags(render_depth, ncam, mjm, active, _CAMOUT_DEPTH, False)
+  seg = _flags(render_seg, ncam, mjm, active, _CAMOUT_SEG, False)
+  assert len(rgb) == ncam and len(depth) == ncam and len(seg) == ncam, (
+    f"render_rgb, render_depth, and render_seg must be a bool or a list of bools with length {ncam}")
+
+  groups = [int(g) for g in enabled_geom_groups]
+  if any(g < 0 or g > 31 for g in groups):
+    raise ValueError(f"create_render_context: enabled_geom_groups must lie in 0..31, got {groups}")
+  group_mask = 0
+  for g in groups:
+    group_mask |= 1 << g
+
+  rgb_adr, depth_adr, seg_adr = -np.ones(ncam, dtype=np.int64), -np.ones(ncam, dtype=np.int64), -np.ones(ncam, dtype=np.int64)
+  ri = di = si = total = 0
+  for i in range(ncam):
+    npix = int(res[i, 0] * res[i, 1])
+    if rgb[i]:
+      rgb_adr[i], ri = ri, ri + npix
+    if depth[i]:
+      depth_adr[i], di = di, di + npix
+    if seg[i]:
+      seg_adr[i], si = si, si + npix
+    total += npix
+  if max(ri, di, si) >= 2**31:
+    raise ValueError("create_render_context: more than 2^31 pixels in one output row")
+
+  # the launch's tile table: cameras whose three outputs are all off get no tiles
+  drawn = [i for i in range(ncam) if rgb[i] or depth[i] or seg[i]]
+  if all(res[i, 0] * res[i, 1] <= 64 for i in drawn):
+    tile_threads, tiles = 64, [(i, 0, 0, 0) for i in drawn]
+  else:
+    tile_threads = 256
+    tiles = [(i, x0, y0, 0) for i in drawn for y0 in range(0, int(res[i, 1]), TILE) for x0 in range(0, int(res[i, 0]), TILE)]
+
+  i32 = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a).astype(np.int32)), device=dev)
+  nl = int(mjm.nlight)
+  return RenderContext(
+    nworld=nworld,
+    nrender=ncam,
+    cam_res=i32(res.reshape(ncam, 2)),
+    cam_id_map=i32(np.asarray(active, dtype=np.int64)),
+    use_textures=bool(use_textures),
+    use_shadows=bool(use_shadows),
+    enabled_geom_groups=groups,
+    group_mask=group_mask,
+    background_color=255 << 24 | 25 << 16 | 25 << 8 | 51,
+    rgb_adr=i32(rgb_adr),
+    depth_adr=i32(depth_adr),
+    seg_adr=i32(seg_adr),
+    render_rgb=torch.as_tensor(rgb, dtype=torch.bool, device=dev).reshape(ncam),
+    render_depth=torch.as_tensor(depth, dtype=torch.bool, device=dev).reshape(ncam),
+    render_seg=torch.as_tensor(seg, dtype=torch.bool, device=dev).reshape(ncam),
+    total_rays=int(total),
+    light_type=i32(np.asarray(getattr(mjm, "light_type", np.zeros(nl))).reshape(-1)[:nl]),
+    light_active=i32(np.asarray(getattr(mjm, "light_active", np.ones(nl))).reshape(-1)[:nl]),
+    light_castshadow=i32(np.asarray(getattr(mjm, "light_castshadow", np.ones(nl))).reshape(-1)[:nl]),
+    tile=i32(np.asarray(tiles, dtype=np.int64).reshape(len(tiles), 4)),
+    tile_threads=tile_threads,
+    rgb_data=torch.zeros((nworld, ri), dtype=torch.int32, device=dev),
+    depth_data=torch.zeros((nworld, di), dtype=torch.float32, device=dev),
+    seg_data=torch.zeros((nworld, max(si, 1)), dtype=torch.int32, device=dev),
+    # host copies for the readers and for validation
+    _res=[(int(w), int(h)) for w, h in res],
+    _adr=dict(rgb=[int(x) for x in rgb_adr], depth=[int(x) for x in depth_adr], seg=[int(x) for x in seg_adr]),
+    _ncam_model=ncam_model,
+    _nlight=nl,
+  )
+
+
+def _crender(rc: RenderContext) -> _lib.CRender:
+  c = _lib.CRender()
+  c.group_mask, c.use_shadows = int(rc.group_mask), int(bool(rc.use_shadows))
+  c.nrender, c.ntile, c.tile_threads = int(rc.nrender), int(rc.tile.shape[0]), int(rc.tile_threads)
+  for name in ("cam_id_map", "cam_res", "rgb_adr", "depth_adr", "seg_adr", "tile", "light_type", "light_active", "light_castshadow"):
+    t = getattr(rc, name)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != rc.rgb_data.device:
+      raise ValueError(f"render: rc.{name} must be a contiguous int32 tensor on {rc.rgb_data.device}")
+    setattr(c, name, t.data_ptr())
+  n = int(rc.nrender)
+  if rc.cam_res.numel() != 2 * n or any(getattr(rc, k).numel() != n for k in ("cam_id_map", "rgb_adr", "depth_adr", "seg_adr")) or rc.tile.dim() != 2 \
+      or rc.tile.shape[1] != 4 or len(rc._res) != n:
+    raise ValueError(f"render: the context's camera tables must hold {n} cameras and its tile table rows of 4")
+  if rc.light_type.numel() != rc._nlight or rc.light_active.numel() != rc._nlight or rc.light_castshadow.numel() != rc._nlight:
+    raise ValueError(f"render: rc.light_type / light_active / light_castshadow must hold {rc._nlight} values")
+  nworld = int(rc.nworld)
+  for name, dtype, ld in (("rgb", torch.int32, "rgb_ld"), ("depth", torch.float32, "depth_ld"), ("seg", torch.int32, "seg_ld")):
+    t = getattr(rc, name + "_data")
+    need = max((a + w * h for a, (w, h) in zip(rc._adr[name], rc._res) if a >= 0), default=0)
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.dim() != 2 or t.shape[0] != nworld or t.shape[1] < need
+        or t.device != rc.rgb_data.device):
+      raise ValueError(f"render: rc.{name}_data must be a contiguous {dtype} tensor of shape ({nworld}, >= {need})")
+    setattr(c, name, t.data_ptr())
+    setattr(c, ld, int(t.shape[1]))
+  return c
+
+
+def render(m: Model, d: Data, rc: RenderContext) -> None:
+  """Renders every camera of the context in every world into rc.rgb_data / rc.depth_data / rc.seg_data
+  (render.py:515-830), in one launch on the Data's stream; capturable in a graph.
+
+  Segmentation: the geom id of the nearest drawn geom, -1 for background.  Depth: the distance along the
+  camera's optical axis, 0 for background.  RGB: mat_rgba (geoms with a material) or geom_rgba, shaded with a
+  hemispheric ambient term and the active lights (directional, point with 1 / (1 + 0.02 r^2), spot with the
+  reference's cone), clamped and packed as a << 24 | r << 16 | g << 8 | b; background (25, 25, 51, 255).  A geom
+  is drawn iff its group is enabled in the context: alpha plays no part.  cam_fovy, cam_intrinsic, geom_rgba
+  and mat_rgba may be batched per world.  The camera, light and geom frames are those of the last position
+  stage (`forward`, `step`, `kinematics` + `camlight`)."""
+  if not isinstance(rc, RenderContext):
+    raise ValueError("render: rc must be a RenderContext from create_render_context")
+  dev = d.qpos.device
+  if int(rc.nworld) != int(d.nworld):
+    raise ValueError(f"render: the render context was made for nworld = {rc.nworld}, the Data has {d.nworld}")
+  if rc.rgb_data.device != dev:
+    raise ValueError(f"render: the render context is on {rc.rgb_data.device}, the Data is on {dev}")
+  if int(rc._ncam_model) != int(m.ncam) or int(rc._nlight) != int(m.nlight):
+    raise ValueError(f"render: the render context was made for a model with {rc._ncam_model} cameras and {rc._nlight} lights, "
+                     f"this one has {m.ncam} and {m.nlight}")
+  from .forward import _stream
+  from .io import cdata, cmodel
+  from .ray import _ray_model
+
+  rm = _ray_model(m)
+  c = _crender(rc)
+  if c.ntile == 0:
+    return
+  rcode = _lib.lib().mjw_render(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), _stream(d))
+  _lib.check(rcode, "mjw_render")
+
+
+def refit_bvh(m: Model, d: Data, rc: RenderContext) -> None:
+  """Does nothing: `render` walks the geoms directly and there is no BVH to refit.  It exists so that code
+  written for the reference (`refit_bvh` before every `render`) runs unchanged."""
+
+
+def _view(rc, camera_index, which, out, shape_tail, dtype, name):
+  if not isinstance(rc, RenderContext):
+    raise ValueError(f"{name}: rc must be a RenderContext")
+  ci = int(camera_index)
+  if ci < 0 or ci >= int(rc.nrender):
+    raise ValueError(f"{name}: camera_index {ci} is not one of the context's {rc.nrender} cameras")
+  adr = rc._adr[which][ci]
+  if adr < 0:
+    raise ValueError(f"{name}: camera {ci} does not render {which} in this context")
+  w, h = rc._res[ci]
+  data = getattr(rc, which + "_data")
+  shape = (int(rc.nworld), h, w) + shape_tail
+  if not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or out.device != data.device:
+    raise ValueError(f"{name}: the output must be a {dtype} tensor of shape {shape} on {data.device}")
+  return data[:, adr : adr + w * h].reshape(int(rc.nworld), h, w)
+
+
+def get_rgb(rc: RenderContext, camera_index: int, rgb_out: torch.Tensor) -> None:
+  """The RGB image of the context's camera `camera_index` (an index into its rendered cameras) as float32
+  (nworld, H, W, 3) in [0, 1], byte / 255."""
+  px = _view(rc, camera_index, "rgb", rgb_out, (3,), torch.float32, "get_rgb")
+  for i, shift in enumerate((16, 8, 0)):
+    rgb_out[..., i] = ((px >> shift) & 0xFF).to(torch.float32) / 255.0
+
+
+def get_depth(rc: RenderContext, camera_index: int, depth_scale: float, depth_out: torch.Tensor) -> None:
+  """clamp(depth / depth_scale, 0, 1) of the context's camera `camera_index` as float32 (nworld, H, W)."""
+  px = _view(rc, camera_index, "depth", depth_out, (), torch.float32, "get_depth")
+  torch.clamp(px / float(depth_scale), 0.0, 1.0, out=depth_out)
+
+
+def get_segmentation(rc: RenderContext, camera_index: int, seg_out: torch.Tensor) -> None:
+  """The geom id per pixel (-1: background) of the context's camera `camera_index` as int32 (nworld, H, W)."""
+  px = _view(rc, camera_index, "seg", seg_out, (), torch.int32, "get_segmentation")
+  seg_out.copy_(px)

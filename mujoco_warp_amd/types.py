@@ -395,6 +395,18 @@ class Data(_Container):
   """Device data.  Field names follow mujoco_warp `types.Data` (types.py:1702-1896)."""
 
 
+class RenderContext(_Container):
+  """What `render` draws and where (reference types.RenderContext, made by `create_render_context`).
+
+  nrender cameras (cam_id_map: their ids in the model; cam_res (nrender, 2): width, height); rgb_adr /
+  depth_adr / seg_adr (nrender,): each camera's first pixel in a row of its output buffer, -1 when that output
+  is off (render_rgb / render_depth / render_seg are the flags); total_rays: pixels of all rendered cameras;
+  light_type / light_active / light_castshadow (nlight,) int32: what `render` reads for the lights.  Buffers,
+  in the reference's layouts: rgb_data (nworld, sum of rgb pixels) int32 holding a << 24 | r << 16 | g << 8 | b,
+  depth_data (nworld, sum of depth pixels) float32, seg_data (nworld, max(sum of seg pixels, 1)) int32.
+  There is no BVH, no texture and no flex state."""
+
+
 class Contact(_Container):
   """Global contact pool (types.py:1617-1655): arrays of length naconmax, filled [0, nacon)."""
 
