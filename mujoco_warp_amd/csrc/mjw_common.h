@@ -18,6 +18,23 @@ constexpr int LPW = 64;   // lanes per world (one wavefront)
 constexpr int CREC = 33;  // words per staged contact record (odd: lane-per-record access is bank-conflict free)
 constexpr int CMAX = 32;  // staged contacts per collision round
 
+// (row, column) of the flat index e = lane, lane + 64, ... over rows of run-time width n, carried by the
+// lane: one division before a copy loop, then a compare-subtract per 64-step instead of a division
+// per element
+struct RowCol {
+  int r, c;
+};
+__device__ __forceinline__ RowCol rc_first(int lane, int n) {
+  RowCol x;
+  x.r = n > 0 ? lane / n : 0;
+  x.c = lane - x.r * n;
+  return x;
+}
+__device__ __forceinline__ void rc_next(RowCol& x, int n) {
+  x.c += LPW;
+  while (x.c >= n) { x.c -= n; x.r++; }
+}
+
 // ST_POOL (with ST_POS): the position stage with the contacts read back from the pool instead of the
 // narrowphase -- the constraint rows after a contactfilter callback edited d.contact (mjw_contact_rows)
 enum : int { ST_POS = 1, ST_VEL = 2, ST_ACT = 4, ST_ACC = 8, ST_SOLVE = 16, ST_EULER = 32, ST_NOFACTOR = 64, ST_POOL = 128 };

@@ -121,6 +121,9 @@ __host__ inline Lay make_layout(const mjw_model_t& m, int njmax, bool nofactor =
     if (nofactor) L.ccd = (usz >= need) ? L.ximat : take(need);
     else L.ccd = (L.qM - L.cdof_dot >= need) ? L.cdof_dot : take(need);
   }
+  // fwd_velocity packs body_level << 16 | index of a word of the nb * 6 cvel / cacc block into one int:
+  // every launcher refuses L.total * 4 > 160 KiB, i.e. more than 40,960 words, so nb * 6 < 65,536 and
+  // nlevel <= nb < 32,768 for every layout that runs
   L.total = o;
   return L;
 }
@@ -151,6 +154,38 @@ struct WS {
   int wid;   // world index within the launch
   int lane;
 };
+
+// n contiguous LDS words to n contiguous global words, lane = consecutive address: the Data outputs
+// whose LDS image is final go out as full-width stores instead of one dword per item lane and component.
+// Call after the barrier that ends the producing step and before the LDS region is reused.
+// Four LDS reads are in flight per pass, so a short array costs one LDS round trip, not one per 64 words.
+__device__ __forceinline__ void block_out(float* dst, const float* src, int n, int lane) {
+#pragma unroll 1
+  for (int e = lane; e < n; e += 4 * LPW) {
+    const bool k1 = e + LPW < n, k2 = e + 2 * LPW < n, k3 = e + 3 * LPW < n;
+    const float v0 = src[e], v1 = k1 ? src[e + LPW] : 0.0f, v2 = k2 ? src[e + 2 * LPW] : 0.0f, v3 = k3 ? src[e + 3 * LPW] : 0.0f;
+    dst[e] = v0;
+    if (k1) dst[e + LPW] = v1;
+    if (k2) dst[e + 2 * LPW] = v2;
+    if (k3) dst[e + 3 * LPW] = v3;
+  }
+}
+
+// acc + p[C * j] for j = j0 .. end - 1 in ascending order (one word of a subtree sum; p points at the
+// word of body 0).  The adds keep their order; four loads are issued ahead of them, so a walk of n bodies
+// costs n / 4 LDS round trips.
+template <int C>
+__device__ __forceinline__ float subtree_sum(float acc, const float* p, int j, int end) {
+  for (; j + 4 <= end; j += 4) {
+    const float x0 = p[C * j], x1 = p[C * (j + 1)], x2 = p[C * (j + 2)], x3 = p[C * (j + 3)];
+    acc += x0;
+    acc += x1;
+    acc += x2;
+    acc += x3;
+  }
+  for (; j < end; j++) acc += p[C * j];
+  return acc;
+}
 
 // -------------------------------------------------------------------------------------------
 // smooth.py: kinematics (smooth.py:44-224, 357-415)
@@ -563,10 +598,9 @@ __device__ __forceinline__ void cholesky(float* A, int n, int nvs, int lane) {
     }
     WSYNC();
   }
-  for (int e = lane; e < n * nvs; e += LPW) {
-    int r = e / nvs, c = e - r * nvs;
-    if (c > r) A[e] = 0.0f;
-  }
+  RowCol x = rc_first(lane, nvs);
+  for (int e = lane; e < n * nvs; e += LPW, rc_next(x, nvs))
+    if (x.c > x.r) A[e] = 0.0f;
   WSYNC();
 }
 
@@ -1538,10 +1572,8 @@ __device__ __forceinline__ void collision_and_constraints(const mjw_model_t& m, 
   const int nrows = min(nefc, njmax);
   if (L.J >= 0) {
     float* gJ = d.efc_J + (long)wid * d.njmax_pad * np;
-    for (int e = lane; e < nrows * np; e += LPW) {
-      int r = e / np, c = e - r * np;
-      gJ[e] = c < nv ? s[L.J + r * nvs + c] : 0.0f;
-    }
+    RowCol x = rc_first(lane, np);
+    for (int e = lane; e < nrows * np; e += LPW, rc_next(x, np)) gJ[e] = x.c < nv ? s[L.J + x.r * nvs + x.c] : 0.0f;
   }
   if (lane == 0) {
     d.ne[wid] = ne;
@@ -1698,6 +1730,12 @@ __device__ __forceinline__ void transmission(const mjw_model_t& m, const mjw_dat
 // POS_LDS: the position stage ran in this launch, so the body / geom frames are in LDS (else they are read
 // from the Data).  PARTS (the stage launches, sub_kernel): bit 0 actuator velocity + com_vel, bit 1 passive,
 // bit 2 tendon bias + rne; the step runs all three
+// Lane map: the per-body 6-vectors that are pure per-component sums (com_vel's local increments and level
+// pass, rne's cacc sums and level pass, the cfrc_int subtree sums) run one lane per (body, component),
+// e = lane, lane + 64, ... with body = e / 6, each lane adding in the order a per-body lane would; the
+// level passes are one pass over all pairs per level.  cdof_dot, the body wrenches (inert_vec, cross
+// products) and qfrc_bias stay one lane per dof / body.  cacc and cfrc_int leave through block_out; cvel and cdof_dot keep
+// their lane-consecutive store loops.
 template <bool TEN, bool POS_LDS, int PARTS = 7>
 __device__ __forceinline__ void fwd_velocity(const mjw_model_t& m, const mjw_data_t& d, const Lay& L, WS& w) {
   const int wid = w.wid, lane = w.lane;
@@ -1724,23 +1762,44 @@ __device__ __forceinline__ void fwd_velocity(const mjw_model_t& m, const mjw_dat
   // and takes cdof_dot = cvel_partial x cdof; the partial sum is split into the parent's cvel
   // (level pass, LDS only) and the body-local part (one pass over dofs in parallel).
   float* dv = s + L.cfrc;  // per-body local increments (cfrc is produced later)
-  for (int b = lane; b < m.nbody; b += LPW) {
-    float acc[6] = {0, 0, 0, 0, 0, 0};
+  // lane = (body, component) for the local sums and the level pass.  The level pass reads each
+  // pair's level and parent word from lvpar (the cacc slots, produced later): one LDS word per pair,
+  // level << 16 | index of the parent's word, level 0 for the world body (never matched)
+  const int nb6 = m.nbody * 6;
+  int* lvpar = si + L.cacc;
+#pragma unroll 1
+  for (int e = lane; e < nb6; e += LPW) {
+    const int b = e / 6, i = e - 6 * b;
+    float acc = 0.0f;
     const int adr = m.body_dofadr[b], num = m.body_dofnum[b];
-    for (int k = adr; k < adr + num; k++)
-      for (int i = 0; i < 6; i++) acc[i] += cd[6 * k + i] * qvel[k];
-    for (int i = 0; i < 6; i++) { dv[6 * b + i] = acc[i]; cvel[6 * b + i] = 0.0f; }
+    for (int k = adr; k < adr + num; k++) acc += cd[6 * k + i] * qvel[k];
+    dv[e] = acc;
+    cvel[e] = 0.0f;
+    lvpar[e] = b > 0 ? (m.body_level[b] << 16 | (6 * m.body_parentid[b] + i)) : 0;
   }
   WSYNC();
-  for (int b0 = 0; b0 < m.nbody; b0 += LPW) {
-    const int b = b0 + lane;
-    const bool ok = b > 0 && b < m.nbody;
-    const int par = ok ? m.body_parentid[b] : 0, lv = ok ? m.body_level[b] : 0;
-    for (int lvl = 1; lvl < m.nlevel; lvl++) {
-      if (ok && lv == lvl)
-        for (int i = 0; i < 6; i++) cvel[6 * b + i] = cvel[6 * par + i] + dv[6 * b + i];
-      WSYNC();
+  // a lane's first four pairs (nbody <= 42; the humanoid has 102 pairs) keep their level / parent word in
+  // registers, so a level costs one LDS round trip; pairs from 256 on read theirs per level
+  int lpr[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) lpr[q] = lane + q * LPW < nb6 ? lvpar[lane + q * LPW] : 0;
+  for (int lvl = 1; lvl < m.nlevel; lvl++) {
+    float par[4], loc[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {  // the reads of a level first (one round trip), then its writes
+      const bool hit = (lpr[q] >> 16) == lvl;
+      par[q] = hit ? cvel[lpr[q] & 0xffff] : 0.0f;
+      loc[q] = hit ? dv[lane + q * LPW] : 0.0f;
     }
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      if ((lpr[q] >> 16) == lvl) cvel[lane + q * LPW] = par[q] + loc[q];
+#pragma unroll 1
+    for (int e = lane + 4 * LPW; e < nb6; e += LPW) {
+      const int lp = lvpar[e];
+      if ((lp >> 16) == lvl) cvel[e] = cvel[lp & 0xffff] + dv[e];
+    }
+    WSYNC();
   }
   // cdof_dot per dof: (cvel[parent] + dofs of the body added before this joint) x cdof;
   // a free joint's rotational dofs also see its translational dofs, which get cdof_dot = 0
@@ -1872,29 +1931,46 @@ __device__ __forceinline__ void fwd_velocity(const mjw_model_t& m, const mjw_dat
     tendon_bias(m, d, wid, lane, qvel, f, cvel, cdof_dot, s + L.scratch, damper);
   }
   // rne (smooth.py:1112-1274, flg_acc = False): cacc[b] = cacc[parent] + sum cdof_dot qvel
-  for (int b = lane; b < m.nbody; b += LPW) {
-    float acc[6] = {0, 0, 0, 0, 0, 0};
+  // lane = (body, component), as in com_vel; the level / parent words go to the cfrc slots here
+  const int nb6 = m.nbody * 6;
+  int* lvpar = si + L.cfrc;
+#pragma unroll 1
+  for (int e = lane; e < nb6; e += LPW) {
+    const int b = e / 6, i = e - 6 * b;
+    float acc = 0.0f;
     if (b == 0) {
       const float* grav = MR(opt_gravity);
-      if (!(m.opt_disableflags & DSBL_GRAVITY))
-        for (int i = 0; i < 3; i++) acc[3 + i] = -grav[i];
+      if (i >= 3 && !(m.opt_disableflags & DSBL_GRAVITY)) acc = -grav[i - 3];
     } else {
       const int adr = m.body_dofadr[b], num = m.body_dofnum[b];
-      for (int k = adr; k < adr + num; k++)
-        for (int i = 0; i < 6; i++) acc[i] += cdof_dot[6 * k + i] * qvel[k];
+      for (int k = adr; k < adr + num; k++) acc += cdof_dot[6 * k + i] * qvel[k];
     }
-    for (int i = 0; i < 6; i++) cacc[6 * b + i] = acc[i];
+    cacc[e] = acc;
+    lvpar[e] = b > 0 ? (m.body_level[b] << 16 | (6 * m.body_parentid[b] + i)) : 0;
   }
   WSYNC();
-  for (int b0 = 0; b0 < m.nbody; b0 += LPW) {
-    const int b = b0 + lane;
-    const bool ok = b > 0 && b < m.nbody;
-    const int par = ok ? m.body_parentid[b] : 0, lv = ok ? m.body_level[b] : 0;
-    for (int lvl = 1; lvl < m.nlevel; lvl++) {
-      if (ok && lv == lvl)
-        for (int i = 0; i < 6; i++) cacc[6 * b + i] += cacc[6 * par + i];
-      WSYNC();
+  // as in com_vel: the level / parent words of a lane's first four pairs in registers, one LDS round
+  // trip per level
+  int lpr[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) lpr[q] = lane + q * LPW < nb6 ? lvpar[lane + q * LPW] : 0;
+  for (int lvl = 1; lvl < m.nlevel; lvl++) {
+    float par[4], loc[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const bool hit = (lpr[q] >> 16) == lvl;
+      par[q] = hit ? cacc[lpr[q] & 0xffff] : 0.0f;
+      loc[q] = hit ? cacc[lane + q * LPW] : 0.0f;
     }
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+      if ((lpr[q] >> 16) == lvl) cacc[lane + q * LPW] = loc[q] + par[q];
+#pragma unroll 1
+    for (int e = lane + 4 * LPW; e < nb6; e += LPW) {
+      const int lp = lvpar[e];
+      if ((lp >> 16) == lvl) cacc[e] += cacc[lp & 0xffff];
+    }
+    WSYNC();
   }
   float* cfrc = s + L.cfrc;
   for (int b = lane; b < m.nbody; b += LPW) {
@@ -1909,18 +1985,16 @@ __device__ __forceinline__ void fwd_velocity(const mjw_model_t& m, const mjw_dat
     for (int i = 0; i < 6; i++) cfrc[6 * b + i] = f[i];
   }
   WSYNC();
-  // backward accumulation = subtree sums; keep result in cvel-sized scratch (cfrc_int)
-  for (int b = lane; b < m.nbody; b += LPW) {
-    float acc[6] = {0, 0, 0, 0, 0, 0};
-    int end = m.body_subtree_end[b];
-    for (int j = (b == 0 ? 1 : b); j < end; j++)
-      for (int i = 0; i < 6; i++) acc[i] += cfrc[6 * j + i];
-    long gb = (long)wid * m.nbody + b;
-    for (int i = 0; i < 6; i++) { d.cfrc_int[gb * 6 + i] = acc[i]; d.cacc[gb * 6 + i] = cacc[6 * b + i]; }
-    // store back into cacc slot? no: qfrc_bias needs cfrc_int of dof bodies -> reuse cdof_dot-free scratch below
-    for (int i = 0; i < 6; i++) s[L.cvel + 6 * b + i] = acc[i];  // cvel no longer needed after this point
+  // backward accumulation = subtree sums; keep result in cvel-sized scratch (cfrc_int);
+  // lane = (body, component), subtree bodies in ascending order
+#pragma unroll 1
+  for (int e = lane; e < nb6; e += LPW) {
+    const int b = e / 6, i = e - 6 * b;
+    s[L.cvel + e] = subtree_sum<6>(0.0f, cfrc + i, b == 0 ? 1 : b, m.body_subtree_end[b]);  // cvel no longer needed after this point
   }
   WSYNC();
+  block_out(d.cfrc_int + (long)wid * nb6, s + L.cvel, nb6, lane);
+  block_out(d.cacc + (long)wid * nb6, cacc, nb6, lane);
   for (int i = lane; i < nv; i += LPW) {
     int b = m.dof_bodyid[i];
     const float* cd = s + L.cdof + 6 * i;
@@ -2001,11 +2075,47 @@ __device__ __forceinline__ void fwd_actuation(const mjw_model_t& m, const mjw_da
     WSYNC();
   }
   const float* jnt_actfrcrange = MR(jnt_actfrcrange);
+  // qfrc_actuator[i] = sum of moment * force over the (actuator, slot) pairs that name dof i, actuators
+  // then slots ascending.  nv <= 64 (dof = lane): instead of every dof lane scanning all nu * amax slots
+  // for its own, the slots push: per round each actuator lane offers its not yet consumed slots to
+  // their dofs by an LDS minimum over the key (actuator << 8 | slot), and the dof lane adds the winner,
+  // so a dof takes its terms in ascending order and the rounds number one more than the most slots any
+  // dof has (2 for one motor per joint).  cand: L.scratch; last: the damper half of L.vec (both free here)
+  // The rounds cost about what a scan of a dozen slots does, so a model with fewer slots keeps the scan
+  // (the order of the terms, and so the value, is the same on both paths).
+  const bool push = nv <= LPW && m.nu * L.amax > 12;
+  float qpush = 0.0f;
+  if (push) {
+    int* cand = si + L.scratch;
+    int* last = si + L.vec + nv;
+    if (lane < nv) last[lane] = -1;
+    for (;;) {
+      if (lane < nv) cand[lane] = 0x7fffffff;
+      WSYNC();
+      for (int a = lane; a < m.nu; a += LPW) {
+        const int nnz = si[L.act_nnz + a];
+        for (int k = 0; k < nnz; k++) {
+          const int dof = si[L.act_momdof + L.amax * a + k], key = a << 8 | k;
+          if (key > last[dof]) atomicMin(&cand[dof], key);
+        }
+      }
+      WSYNC();
+      const int key = lane < nv ? cand[lane] : 0x7fffffff;
+      const bool hit = key != 0x7fffffff;
+      if (__ballot(hit) == 0) break;
+      if (hit) {
+        const int a = key >> 8, k = key & 255;
+        qpush += s[L.act_mom + L.amax * a + k] * s[L.act_force + a];
+        last[lane] = key;
+      }
+    }
+  }
   for (int i = lane; i < nv; i += LPW) {
-    float q = 0.0f;
-    for (int a = 0; a < m.nu; a++)
-      for (int k = 0; k < si[L.act_nnz + a]; k++)
-        if (si[L.act_momdof + L.amax * a + k] == i) q += s[L.act_mom + L.amax * a + k] * s[L.act_force + a];
+    float q = qpush;
+    if (!push)
+      for (int a = 0; a < m.nu; a++)
+        for (int k = 0; k < si[L.act_nnz + a]; k++)
+          if (si[L.act_momdof + L.amax * a + k] == i) q += s[L.act_mom + L.amax * a + k] * s[L.act_force + a];
     int j = m.dof_jntid[i];
     // forward.py:824-826: actuator-level gravity compensation
     if (TEN && m.ngravcomp && m.jnt_actgravcomp[j]) q += VEL_LDS ? s[L.vec + i] : d.qfrc_gravcomp[(long)wid * nv + i];
@@ -2035,12 +2145,11 @@ __device__ __forceinline__ void fwd_acceleration(const mjw_model_t& m, const mjw
     for (int k = 0; k < 3; k++) { Wb[6 * b + k] = xfrc[6 * b + 3 + k] + c[k]; Wb[6 * b + 3 + k] = f[k]; }
   }
   WSYNC();
-  for (int b = lane; b < m.nbody; b += LPW) {
-    float acc[6] = {0, 0, 0, 0, 0, 0};
-    const int end = m.body_subtree_end[b];
-    for (int j = b; j < end; j++)
-      for (int k = 0; k < 6; k++) acc[k] += Wb[6 * j + k];
-    for (int k = 0; k < 6; k++) Ws[6 * b + k] = acc[k];
+  // lane = (body, component), subtree bodies in ascending order
+#pragma unroll 1
+  for (int e = lane; e < m.nbody * 6; e += LPW) {
+    const int b = e / 6, k = e - 6 * b;
+    Ws[e] = subtree_sum<6>(0.0f, Wb + k, b, m.body_subtree_end[b]);
   }
   WSYNC();
   float qs = 0.0f;
@@ -2066,10 +2175,8 @@ __device__ __forceinline__ void fwd_acceleration(const mjw_model_t& m, const mjw
     d.qacc_smooth[(long)wid * nv + lane] = qacc_smooth;
   }
   float* gL = d.qLD + (long)wid * nv * nv;
-  for (int e = lane; e < nv * nv; e += LPW) {
-    int r = e / nv, c = e - r * nv;
-    gL[e] = Lm[r * nvs + c];
-  }
+  RowCol x = rc_first(lane, nv);
+  for (int e = lane; e < nv * nv; e += LPW, rc_next(x, nv)) gL[e] = Lm[x.r * nvs + x.c];
   WSYNC();
 }
 
@@ -2487,10 +2594,9 @@ __device__ __forceinline__ void euler(const mjw_model_t& m, const mjw_data_t& d,
     const float* dof_damping = MR(dof_damping);
     const bool damp = !(fl & DSBL_DAMPER);
     float* Lm = s + L.L;
-    for (int e = lane; e < nv * nvs; e += LPW) {
-      int r = e / nvs, c = e - r * nvs;
-      Lm[e] = s[L.qM + e] + ((damp && r == c && r < nv) ? dt * dof_damping[r] : 0.0f);
-    }
+    RowCol x = rc_first(lane, nvs);
+    for (int e = lane; e < nv * nvs; e += LPW, rc_next(x, nvs))
+      Lm[e] = s[L.qM + e] + ((damp && x.r == x.c && x.r < nv) ? dt * dof_damping[x.r] : 0.0f);
     WSYNC();
     if (implicitfast && m.nu > 0 && !(fl & DSBL_ACTUATION)) {
       for (int u = 0; u < m.nu; u++) {
@@ -2609,10 +2715,8 @@ __device__ __forceinline__ void load_smooth(const mjw_model_t& m, const mjw_data
     }
   }
   if ((stages & (ST_ACC | ST_SOLVE | ST_EULER)) && !(stages & ST_POS) && !(stages & ST_NOFACTOR)) {
-    for (int e = lane; e < nv * nvs; e += LPW) {
-      int r = e / nvs, c = e - r * nvs;
-      s[L.qM + e] = c < nv ? d.qM[(long)wid * np * np + r * np + c] : 0.0f;
-    }
+    RowCol x = rc_first(lane, nvs);
+    for (int e = lane; e < nv * nvs; e += LPW, rc_next(x, nvs)) s[L.qM + e] = x.c < nv ? d.qM[(long)wid * np * np + x.r * np + x.c] : 0.0f;
   }
   if ((stages & ST_ACC) && !(stages & ST_VEL)) {
     for (int i = lane; i < nv; i += LPW) {
@@ -2625,10 +2729,8 @@ __device__ __forceinline__ void load_smooth(const mjw_model_t& m, const mjw_data
     for (int i = lane; i < nv; i += LPW) s[L.qfrc_actuator + i] = d.qfrc_actuator[(long)wid * nv + i];
   }
   if ((stages & ST_SOLVE) && !(stages & ST_ACC)) {
-    for (int e = lane; e < nv * nvs; e += LPW) {
-      int r = e / nvs, c = e - r * nvs;
-      s[L.L + e] = (c < nv) ? d.qLD[(long)wid * nv * nv + r * nv + c] : 0.0f;
-    }
+    RowCol x = rc_first(lane, nvs);
+    for (int e = lane; e < nv * nvs; e += LPW, rc_next(x, nvs)) s[L.L + e] = (x.c < nv) ? d.qLD[(long)wid * nv * nv + x.r * nv + x.c] : 0.0f;
     for (int i = lane; i < nv; i += LPW) {
       long gi = (long)wid * nv + i;
       s[L.qfrc_smooth + i] = d.qfrc_smooth[gi];
@@ -2638,10 +2740,8 @@ __device__ __forceinline__ void load_smooth(const mjw_model_t& m, const mjw_data
   if ((stages & ST_SOLVE) && !(stages & ST_POS)) {
     int nefc = d.nefc[wid];
     int nrows = min(nefc, d.njmax);
-    for (int e = lane; e < nrows * nvs; e += LPW) {
-      int r = e / nvs, c = e - r * nvs;
-      s[L.J + e] = c < nv ? d.efc_J[(long)wid * d.njmax_pad * np + r * np + c] : 0.0f;
-    }
+    RowCol x = rc_first(lane, nvs);
+    for (int e = lane; e < nrows * nvs; e += LPW, rc_next(x, nvs)) s[L.J + e] = x.c < nv ? d.efc_J[(long)wid * d.njmax_pad * np + x.r * np + x.c] : 0.0f;
     for (int r = lane; r < nrows; r += LPW) {
       long gr = (long)wid * d.njmax + r;
       s[L.efc_D + r] = d.efc_D[(long)wid * d.njmax_pad + r];
@@ -2809,10 +2909,8 @@ __device__ __forceinline__ void load_pos_fields(const mjw_model_t& m, const mjw_
   cp(L.crb, d.crb + wid * nb * 10, nb * 10);
   cp(L.cdof, d.cdof + wid * nv * 6, nv * 6);
   const int nvs = L.nvs, np = m.nv_pad;
-  for (long e = lane; e < nv * nvs; e += LPW) {
-    const int r = (int)(e / nvs), c = (int)(e - (long)r * nvs);
-    s[L.qM + e] = c < nv ? d.qM[(long)wid * np * np + r * np + c] : 0.0f;
-  }
+  RowCol x = rc_first(lane, nvs);
+  for (int e = lane; e < (int)nv * nvs; e += LPW, rc_next(x, nvs)) s[L.qM + e] = x.c < nv ? d.qM[(long)wid * np * np + x.r * np + x.c] : 0.0f;
 }
 
 // SUB_*: the stage a sub_kernel launch runs (include/mjw_amd.h MJW_STAGE_*)
