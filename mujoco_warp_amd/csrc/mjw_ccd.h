@@ -1436,4 +1436,42 @@ __device__ __forceinline__ int hfield_pair(const CcdWS& w, int epa_it, float tol
   return n;
 }
 
+// ---- one convex pair's model-derived arguments.  The caller keeps its barriers and its record write-out;
+// gxpos / gxmat are the world's geom frames, wherever they live -----------------------------------------
+// the pair's contact margin: an explicit <pair> (pid > -1) has its own (collision_core.py:271)
+__device__ __forceinline__ float pair_margin(const mjw_model_t& m, int wid, int pid, int g1, int g2) {
+  const float* gmargin = MR(geom_margin);
+  return pid > -1 ? MR(pair_margin)[pid] : gmargin[g1] + gmargin[g2];
+}
+
+// the pair's two geoms into the lockstep workspace (meshes with their vertex ranges)
+__device__ __forceinline__ void put_pair_geoms(const mjw_model_t& m, float* W, const CcdLay& CL, const float* gxpos, const float* gxmat,
+                                               const float* gsize, int g1, int g2) {
+  const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
+  const int md1 = t1 == GEOM_MESH ? m.geom_dataid[g1] : -1, md2 = t2 == GEOM_MESH ? m.geom_dataid[g2] : -1;
+  put_cgeom(W + CL.geoms, gxpos + 3 * g1, gxmat + 9 * g1, gsize + 3 * g1, t1, md1 >= 0 ? m.mesh_vertadr[md1] : 0,
+            md1 >= 0 ? m.mesh_vertnum[md1] : 0, md1);
+  put_cgeom(W + CL.geoms + CGEOM_WORDS, gxpos + 3 * g2, gxmat + 9 * g2, gsize + 3 * g2, t2, md2 >= 0 ? m.mesh_vertadr[md2] : 0,
+            md2 >= 0 ? m.mesh_vertnum[md2] : 0, md2);
+}
+
+// ccd_pair on the geoms put_pair_geoms left in W, with the model's iteration counts, tolerance and multi-contact bounds
+__device__ __forceinline__ int ccd_pair_of(const mjw_model_t& m, int wid, float* W, float margin, float cutoff, const MeshPoly& MP) {
+  return ccd_pair(W, m.ccd_epa_iterations, MR(opt_ccd_tolerance)[0], m.opt_ccd_iterations, margin, MR(mesh_vert), cutoff, &MP,
+                  (m.opt_enableflags & ENBL_MULTICCD) != 0, m.nmaxpolygon, m.nmaxmeshdeg);
+}
+
+// hfield_pair of heightfield geom g1 against geom g2 (pid: the explicit pair or -1); the record goes to `out`
+__device__ __forceinline__ int hfield_pair_of(const mjw_model_t& m, int wid, const CcdWS& cw, const float* gxpos, const float* gxmat, int g1,
+                                              int g2, int pid, float* out) {
+  const float* gmargin = MR(geom_margin);
+  const float* mesh_vert = MR(mesh_vert);
+  const int hid = m.geom_dataid[g1], t2 = m.geom_type[g2], md2 = t2 == GEOM_MESH ? m.geom_dataid[g2] : -1;
+  return hfield_pair(cw, m.ccd_epa_iterations, MR(opt_ccd_tolerance)[0], m.opt_ccd_iterations, gmargin[g1] + gmargin[g2],
+                     pair_margin(m, wid, pid, g1, g2), gxpos + 3 * g1, gxmat + 9 * g1, MR(hfield_size) + 4 * hid, m.hfield_nrow[hid],
+                     m.hfield_ncol[hid], MR(hfield_data) + m.hfield_adr[hid], gxpos + 3 * g2, gxmat + 9 * g2, MR(geom_size) + 3 * g2,
+                     MR(geom_rbound)[g2], t2, md2 >= 0 ? mesh_vert + 3 * (long)m.mesh_vertadr[md2] : nullptr,
+                     md2 >= 0 ? m.mesh_vertnum[md2] : 0, out);
+}
+
 }  // namespace mjw

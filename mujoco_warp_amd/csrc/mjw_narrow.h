@@ -571,4 +571,93 @@ __device__ __forceinline__ float sphere_cylinder(float* pos, float* nrm, const f
   return sphere_sphere(pos, nrm, sp, sr, corner, 0.0f);
 }
 
+// -------------------------------------------------------------------------------------------
+// per-pair functions over one world's geom frames (gxpos / gxmat: LDS in the fused kernels, HBM in the
+// sparse kernels and the stand-alone collision entry points); the caller keeps its loop and its stores
+// -------------------------------------------------------------------------------------------
+// collision_driver.py:274-321
+__device__ __forceinline__ bool broadphase_filter(const mjw_model_t& m, int wid, const float* gxpos, const float* gxmat, int g1, int g2) {
+  const float* geom_aabb = MR(geom_aabb);
+  const float* geom_rbound = MR(geom_rbound);
+  const float* geom_margin = MR(geom_margin);
+  float rb1 = geom_rbound[g1], rb2 = geom_rbound[g2];
+  float mg1 = geom_margin[g1], mg2 = geom_margin[g2];
+  const float* xp1 = gxpos + 3 * g1;
+  const float* xp2 = gxpos + 3 * g2;
+  const float* xm1 = gxmat + 9 * g1;
+  const float* xm2 = gxmat + 9 * g2;
+  int filt = m.opt_broadphase_filter;
+  if (rb1 == 0.0f || rb2 == 0.0f) {
+    if (filt & FILTER_PLANE) {
+      if (rb1 == 0.0f) {
+        float dif[3] = {xp2[0] - xp1[0], xp2[1] - xp1[1], xp2[2] - xp1[2]}, n[3] = {xm1[2], xm1[5], xm1[8]};
+        return dot3(dif, n) <= rb2 + mg1 + mg2;
+      } else {
+        float dif[3] = {xp1[0] - xp2[0], xp1[1] - xp2[1], xp1[2] - xp2[2]}, n[3] = {xm2[2], xm2[5], xm2[8]};
+        return dot3(dif, n) <= rb1 + mg1 + mg2;
+      }
+    }
+    return true;
+  }
+  if (filt & FILTER_SPHERE) {
+    float bound = rb1 + rb2 + mg1 + mg2;
+    float dif[3] = {xp2[0] - xp1[0], xp2[1] - xp1[1], xp2[2] - xp1[2]};
+    if (!(dot3(dif, dif) <= bound * bound)) return false;
+  }
+  if (filt & FILTER_AABB)
+    if (!aabb_filter(geom_aabb + 6 * g1, geom_aabb + 6 * g2, geom_aabb + 6 * g1 + 3, geom_aabb + 6 * g2 + 3, mg1 + mg2, xp1, xp2, xm1, xm2))
+      return false;
+  if (filt & FILTER_OBB)
+    if (!obb_filter(geom_aabb + 6 * g1, geom_aabb + 6 * g2, geom_aabb + 6 * g1 + 3, geom_aabb + 6 * g2 + 3, mg1 + mg2, xp1, xp2, xm1, xm2))
+      return false;
+  return true;
+}
+
+// narrowphase of one type-sorted pair with up to two points (collision_primitive.py:280-662)
+// BOX = false compiles out the pairs with a box (sphere-box, capsule-box; plane-box and box-box are
+// handled by the caller): models without boxes then run a kernel with 118 instead of 128+ VGPRs and
+// no scratch spills
+template <bool BOX>
+__device__ __forceinline__ void primitive_pair(const mjw_model_t& m, int wid, const float* gxpos, const float* gxmat, int g1, int g2, float margin,
+                                               Con2& c) {
+  const float* geom_size = MR(geom_size);
+  int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
+  const float* p1 = gxpos + 3 * g1;
+  const float* p2 = gxpos + 3 * g2;
+  const float* r1 = gxmat + 9 * g1;
+  const float* r2 = gxmat + 9 * g2;
+  const float* s1 = geom_size + 3 * g1;
+  const float* s2 = geom_size + 3 * g2;
+  float n1[3] = {r1[2], r1[5], r1[8]}, n2[3] = {r2[2], r2[5], r2[8]};
+  c.n = 0;
+  if (t1 == GEOM_PLANE && t2 == GEOM_SPHERE) {
+    c.dist[0] = plane_sphere(c.pos[0], n1, p1, p2, s2[0]);
+    make_frame(c.frame[0], n1);
+    c.n = 1;
+  } else if (t1 == GEOM_PLANE && t2 == GEOM_CAPSULE) {
+    plane_capsule(c, n1, p1, p2, n2, s2[0], s2[1]);
+  } else if (t1 == GEOM_SPHERE && t2 == GEOM_SPHERE) {
+    float nrm[3];
+    c.dist[0] = sphere_sphere(c.pos[0], nrm, p1, s1[0], p2, s2[0]);
+    make_frame(c.frame[0], nrm);
+    c.n = 1;
+  } else if (t1 == GEOM_SPHERE && t2 == GEOM_CAPSULE) {
+    float a[3], b[3], pt[3], nrm[3];
+    for (int i = 0; i < 3; i++) { a[i] = p2[i] - n2[i] * s2[1]; b[i] = p2[i] + n2[i] * s2[1]; }
+    closest_segment_point(pt, a, b, p1);
+    c.dist[0] = sphere_sphere(c.pos[0], nrm, p1, s1[0], pt, s2[0]);
+    make_frame(c.frame[0], nrm);
+    c.n = 1;
+  } else if (t1 == GEOM_CAPSULE && t2 == GEOM_CAPSULE) {
+    capsule_capsule(c, p1, n1, s1[0], s1[1], p2, n2, s2[0], s2[1], margin);
+  } else if (BOX && t1 == GEOM_SPHERE && t2 == GEOM_BOX) {  // collision_primitive.py:1047-1114
+    float nrm[3];
+    c.dist[0] = sphere_box(c.pos[0], nrm, p1, s1[0], p2, r2, s2);
+    make_frame(c.frame[0], nrm);
+    c.n = 1;
+  } else if (BOX && t1 == GEOM_CAPSULE && t2 == GEOM_BOX) {  // collision_primitive.py:1117-1199
+    capsule_box(c, p1, n1, s1[0], s1[1], p2, r2, s2);
+  }
+}
+
 }  // namespace mjw

@@ -366,8 +366,7 @@ __device__ __forceinline__ void coll_offer(CollBest& b, float dist, const float*
 // (record e: convex pairs read the result the wave computed in lockstep, sensor_convex_records)
 __device__ void coll_pair(const mjw_model_t& m, int wid, const Frames& F, int g1, int g2, int pairid, bool flip, CollBest& b, int e) {
   const float* geom_size = MR(geom_size);
-  const float* gmargin = MR(geom_margin);
-  const float margin = pairid > -1 ? MR(pair_margin)[pairid] : gmargin[g1] + gmargin[g2];
+  const float margin = pair_margin(m, wid, pairid, g1, g2);
   const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
   if (sensor_convex(t1, t2) || t1 == GEOM_HFIELD) {
     const float* q = F.scc + SCC_WORDS * e;
@@ -398,40 +397,16 @@ __device__ void coll_pair(const mjw_model_t& m, int wid, const Frames& F, int g1
     return;
   }
   Con2 c;
-  c.n = 0;
-  if (t1 == GEOM_PLANE && t2 == GEOM_SPHERE) {
-    c.dist[0] = plane_sphere(c.pos[0], n1, p1, p2, s2[0]);
-    make_frame(c.frame[0], n1);
-    c.n = 1;
-  } else if (t1 == GEOM_PLANE && t2 == GEOM_CAPSULE) {
-    plane_capsule(c, n1, p1, p2, n2, s2[0], s2[1]);
-  } else if (t1 == GEOM_PLANE && t2 == GEOM_ELLIPSOID) {
+  if (t1 == GEOM_PLANE && t2 == GEOM_ELLIPSOID) {
     c.dist[0] = plane_ellipsoid(c.pos[0], n1, p1, p2, r2, s2);
     make_frame(c.frame[0], n1);
-    c.n = 1;
-  } else if (t1 == GEOM_SPHERE && t2 == GEOM_SPHERE) {
-    c.dist[0] = sphere_sphere(c.pos[0], nrm, p1, s1[0], p2, s2[0]);
-    make_frame(c.frame[0], nrm);
-    c.n = 1;
-  } else if (t1 == GEOM_SPHERE && t2 == GEOM_CAPSULE) {
-    float a[3], bb[3], pt[3];
-    for (int i = 0; i < 3; i++) { a[i] = p2[i] - n2[i] * s2[1]; bb[i] = p2[i] + n2[i] * s2[1]; }
-    closest_segment_point(pt, a, bb, p1);
-    c.dist[0] = sphere_sphere(c.pos[0], nrm, p1, s1[0], pt, s2[0]);
-    make_frame(c.frame[0], nrm);
     c.n = 1;
   } else if (t1 == GEOM_SPHERE && t2 == GEOM_CYLINDER) {
     c.dist[0] = sphere_cylinder(c.pos[0], nrm, p1, s1[0], p2, n2, s2[0], s2[1]);
     make_frame(c.frame[0], nrm);
     c.n = 1;
-  } else if (t1 == GEOM_SPHERE && t2 == GEOM_BOX) {
-    c.dist[0] = sphere_box(c.pos[0], nrm, p1, s1[0], p2, r2, s2);
-    make_frame(c.frame[0], nrm);
-    c.n = 1;
-  } else if (t1 == GEOM_CAPSULE && t2 == GEOM_CAPSULE) {
-    capsule_capsule(c, p1, n1, s1[0], s1[1], p2, n2, s2[0], s2[1], margin);
-  } else if (t1 == GEOM_CAPSULE && t2 == GEOM_BOX) {
-    capsule_box(c, p1, n1, s1[0], s1[1], p2, r2, s2);
+  } else {
+    primitive_pair<true>(m, wid, F.gxpos, F.gxmat, g1, g2, margin, c);
   }
   for (int i = 0; i < c.n && i < 2; i++) coll_offer(b, c.dist[i], c.pos[i], c.frame[i], flip);
 }
@@ -445,8 +420,6 @@ __device__ void coll_pair(const mjw_model_t& m, int wid, const Frames& F, int g1
 // margins.  Separate from the lane-per-sensor loop.
 __device__ void sensor_convex_records(const mjw_model_t& m, const Frames& F, int wid, float* W, float* out) {
   const float* gsize = MR(geom_size);
-  const float* gmargin = MR(geom_margin);
-  const float* mesh_vert = MR(mesh_vert);
   const CcdLay CL = ccd_layout(m.ccd_epa_iterations, m.nhfield > 0, m.nmaxpolygon, m.nmaxmeshdeg);
   const MeshPoly MP = mesh_poly(m);
   const int lane = (int)(threadIdx.x & 63);
@@ -458,18 +431,11 @@ __device__ void sensor_convex_records(const mjw_model_t& m, const Frames& F, int
       const int* r = m.sensor_collision_pair + 4 * e;
       const int g1 = r[0], g2 = r[1], t1 = m.geom_type[g1], t2 = m.geom_type[g2];
       if (!sensor_convex(t1, t2) && t1 != GEOM_HFIELD) continue;
-      const int md1 = t1 == GEOM_MESH ? m.geom_dataid[g1] : -1, md2 = t2 == GEOM_MESH ? m.geom_dataid[g2] : -1;
-      const float margin = r[2] > -1 ? MR(pair_margin)[r[2]] : gmargin[g1] + gmargin[g2];
       if (t1 == GEOM_HFIELD) {
-        const int hid = m.geom_dataid[g1];
         CcdWS cw;
         cw.W = W;
         cw.L = CL;
-        const int n = hfield_pair(cw, m.ccd_epa_iterations, MR(opt_ccd_tolerance)[0], m.opt_ccd_iterations, gmargin[g1] + gmargin[g2],
-                                  margin, F.gxpos + 3 * g1, F.gxmat + 9 * g1, MR(hfield_size) + 4 * hid, m.hfield_nrow[hid],
-                                  m.hfield_ncol[hid], MR(hfield_data) + m.hfield_adr[hid], F.gxpos + 3 * g2, F.gxmat + 9 * g2,
-                                  gsize + 3 * g2, MR(geom_rbound)[g2], t2, md2 >= 0 ? mesh_vert + 3 * (long)m.mesh_vertadr[md2] : nullptr,
-                                  md2 >= 0 ? m.mesh_vertnum[md2] : 0, W + CL.out);
+        const int n = hfield_pair_of(m, wid, cw, F.gxpos, F.gxmat, g1, g2, r[2], W + CL.out);
         if (lane == 0) {
           const float* o = W + CL.out;
           float* q = out + SCC_WORDS * e;
@@ -482,13 +448,9 @@ __device__ void sensor_convex_records(const mjw_model_t& m, const Frames& F, int
         __syncthreads();
         continue;
       }
-      put_cgeom(W + CL.geoms, F.gxpos + 3 * g1, F.gxmat + 9 * g1, gsize + 3 * g1, t1, md1 >= 0 ? m.mesh_vertadr[md1] : 0,
-                md1 >= 0 ? m.mesh_vertnum[md1] : 0, md1);
-      put_cgeom(W + CL.geoms + CGEOM_WORDS, F.gxpos + 3 * g2, F.gxmat + 9 * g2, gsize + 3 * g2, t2, md2 >= 0 ? m.mesh_vertadr[md2] : 0,
-                md2 >= 0 ? m.mesh_vertnum[md2] : 0, md2);
+      put_pair_geoms(m, W, CL, F.gxpos, F.gxmat, gsize, g1, g2);
       __syncthreads();
-      const int nc = ccd_pair(W, m.ccd_epa_iterations, MR(opt_ccd_tolerance)[0], m.opt_ccd_iterations, margin, mesh_vert, 1.0e32f, &MP,
-                              (m.opt_enableflags & ENBL_MULTICCD) != 0, m.nmaxpolygon, m.nmaxmeshdeg);
+      const int nc = ccd_pair_of(m, wid, W, pair_margin(m, wid, r[2], g1, g2), 1.0e32f, MP);
       if (lane == 0) {
         const float* o = W + CL.out;
         float nrm[3] = {o[1], o[2], o[3]};

@@ -866,37 +866,10 @@ __device__ __forceinline__ void mul_m_trees(const mjw_model_t& m, const float* M
 // collision: geom pairs (collision_driver.py:697-789 + primitive narrowphase), flex triangles vs
 // geoms (collision_flex.py:381-529) and flex vertices vs planes (:261-378)
 // ---------------------------------------------------------------------------------------------
-// collision_driver.py:274-321 on global frames
+// broadphase_filter (mjw_narrow.h) as a function of its own: force-inlined into collide_item's three call sites it
+// cost forward_kernel<1024> 1088 B/lane of scratch (profiles/r09_resources_tried.txt)
 __device__ bool broadphase(const mjw_model_t& m, int wid, const float* gx, const float* gm, int g1, int g2) {
-  const float* geom_aabb = MR(geom_aabb);
-  const float* geom_rbound = MR(geom_rbound);
-  const float* geom_margin = MR(geom_margin);
-  const float rb1 = geom_rbound[g1], rb2 = geom_rbound[g2], mg1 = geom_margin[g1], mg2 = geom_margin[g2];
-  const float *xp1 = gx + 3 * g1, *xp2 = gx + 3 * g2, *xm1 = gm + 9 * g1, *xm2 = gm + 9 * g2;
-  const int filt = m.opt_broadphase_filter;
-  if (rb1 == 0.0f || rb2 == 0.0f) {
-    if (filt & FILTER_PLANE) {
-      if (rb1 == 0.0f) {
-        float dif[3] = {xp2[0] - xp1[0], xp2[1] - xp1[1], xp2[2] - xp1[2]}, n[3] = {xm1[2], xm1[5], xm1[8]};
-        return dot3(dif, n) <= rb2 + mg1 + mg2;
-      }
-      float dif[3] = {xp1[0] - xp2[0], xp1[1] - xp2[1], xp1[2] - xp2[2]}, n[3] = {xm2[2], xm2[5], xm2[8]};
-      return dot3(dif, n) <= rb1 + mg1 + mg2;
-    }
-    return true;
-  }
-  if (filt & FILTER_SPHERE) {
-    const float bound = rb1 + rb2 + mg1 + mg2;
-    float dif[3] = {xp2[0] - xp1[0], xp2[1] - xp1[1], xp2[2] - xp1[2]};
-    if (!(dot3(dif, dif) <= bound * bound)) return false;
-  }
-  if (filt & FILTER_AABB)
-    if (!aabb_filter(geom_aabb + 6 * g1, geom_aabb + 6 * g2, geom_aabb + 6 * g1 + 3, geom_aabb + 6 * g2 + 3, mg1 + mg2, xp1, xp2, xm1, xm2))
-      return false;
-  if (filt & FILTER_OBB)
-    if (!obb_filter(geom_aabb + 6 * g1, geom_aabb + 6 * g2, geom_aabb + 6 * g1 + 3, geom_aabb + 6 * g2 + 3, mg1 + mg2, xp1, xp2, xm1, xm2))
-      return false;
-  return true;
+  return broadphase_filter(m, wid, gx, gm, g1, g2);
 }
 
 struct ConOut {
@@ -937,7 +910,7 @@ __device__ void write_contact(const mjw_model_t& m, const mjw_data_t& d, int wid
   d.contact_geomcollisionid[slot] = 0;
 }
 
-// out-of-line copies of the (force-inlined, shared with the dense kernel) primitive narrowphase:
+// out-of-line copies of the (force-inlined, mjw_narrow.h) primitive narrowphase functions:
 // collide_item runs three ways per step, and inlining every pair type into it spilled to scratch
 __device__ __noinline__ void nl_capsule_capsule(Con2& c, const float* p1, const float* n1, float r1, float h1, const float* p2,
                                                 const float* n2, float r2, float h2, float margin) {
@@ -1778,36 +1751,8 @@ __device__ int make_rows(const mjw_model_t& m, const mjw_data_t& d, int wid, int
     }
     d.efc_J_rownnz[(long)wid * njmax + r] = nnz;
     const int type = condim == 1 ? CNSTR_CONTACT_FRICTIONLESS : CNSTR_CONTACT_PYRAMIDAL;
-    const float* sr = d.contact_solref + 2 * (long)i;
-    const float* si = d.contact_solimp + 5 * (long)i;
-    // same scalar math as put_row, keeping the J row written above
-    const float timestep = MR(opt_timestep)[0];
-    float timeconst = sr[0], dampratio = sr[1];
-    float dmin = si[0], dmax = si[1], width = si[2], mid = si[3], power = si[4];
-    if (!(m.opt_disableflags & DSBL_REFSAFE)) timeconst = fmaxf(timeconst, 2.0f * timestep);
-    dmin = clampf(dmin, MJW_MINIMP, MJW_MAXIMP);
-    dmax = clampf(dmax, MJW_MINIMP, MJW_MAXIMP);
-    width = fmaxf(MJW_MINVAL, width);
-    mid = clampf(mid, MJW_MINIMP, MJW_MAXIMP);
-    power = fmaxf(1.0f, power);
-    const float dmax_sq = dmax * dmax;
-    float kk = 1.0f / (dmax_sq * timeconst * timeconst * dampratio * dampratio);
-    float bb = 2.0f / (dmax * timeconst);
-    if (sr[0] <= 0.0f) kk = -sr[0] / dmax_sq;
-    if (sr[1] <= 0.0f) bb = -sr[1] / dmax;
-    const float imp_x = fabsf(pos) / width;
-    float imp = dmin + imp_shape(imp_x, mid, power) * (dmax - dmin);
-    imp = clampf(imp, dmin, dmax);
-    if (imp_x > 1.0f) imp = dmax;
-    const long gr = (long)wid * njmax + r;
-    d.efc_D[(long)wid * d.njmax_pad + r] = 1.0f / fmaxf(invweight * (1.0f - imp) / imp, MJW_MINVAL);
-    d.efc_vel[gr] = vel;
-    d.efc_aref[gr] = -kk * imp * pos - bb * vel;
-    d.efc_pos[gr] = pos + includemargin;
-    d.efc_margin[gr] = includemargin;
-    d.efc_frictionloss[gr] = 0.0f;
-    d.efc_type[gr] = type;
-    d.efc_id[gr] = i;
+    put_row_scalars(m, d, wid, r, vel, pos, pos, invweight, d.contact_solref + 2 * (long)i, d.contact_solimp + 5 * (long)i, includemargin, 0.0f,
+                    type, i);
   }
   return nrow;
 }
@@ -2484,8 +2429,6 @@ __device__ __forceinline__ void ccd_body(const mjw_model_t& m, const mjw_data_t&
   const float* gx = d.geom_xpos + (long)wid * m.ngeom * 3;
   const float* gm = d.geom_xmat + (long)wid * m.ngeom * 9;
   const float* gsize = MR(geom_size);
-  const float* gmargin = MR(geom_margin);
-  const float* mesh_vert = MR(mesh_vert);
   for (int p0 = 0; p0 < m.nxn; p0 += 64) {
     const int p = p0 + lane;
     bool pass = false;
@@ -2498,33 +2441,21 @@ __device__ __forceinline__ void ccd_body(const mjw_model_t& m, const mjw_data_t&
     for (int k = 0; k < nsurv; k++) {
       const int q = list[k];
       const int g1 = m.nxn_geom_pair[2 * q], g2 = m.nxn_geom_pair[2 * q + 1];
-      const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
-      const int md1 = t1 == GEOM_MESH ? m.geom_dataid[g1] : -1, md2 = t2 == GEOM_MESH ? m.geom_dataid[g2] : -1;
+      const int t1 = m.geom_type[g1];
       if (HF && t1 == GEOM_HFIELD) {
         // heightfield-convex pair (collision_convex.py:158-697): the record is built whole in the workspace
-        const int hid = m.geom_dataid[g1], pid = m.nxn_pairid[2 * q];
         CcdWS cw;
         cw.W = W;
         cw.L = CL;
-        hfield_pair(cw, m.ccd_epa_iterations, MR(opt_ccd_tolerance)[0], m.opt_ccd_iterations, gmargin[g1] + gmargin[g2],
-                    pid > -1 ? MR(pair_margin)[pid] : gmargin[g1] + gmargin[g2], gx + 3 * g1, gm + 9 * g1, MR(hfield_size) + 4 * hid,
-                    m.hfield_nrow[hid], m.hfield_ncol[hid], MR(hfield_data) + m.hfield_adr[hid], gx + 3 * g2, gm + 9 * g2, gsize + 3 * g2,
-                    MR(geom_rbound)[g2], t2, md2 >= 0 ? mesh_vert + 3 * (long)m.mesh_vertadr[md2] : nullptr,
-                    md2 >= 0 ? m.mesh_vertnum[md2] : 0, W + CL.out);
+        hfield_pair_of(m, wid, cw, gx, gm, g1, g2, m.nxn_pairid[2 * q], W + CL.out);
         float* out = d.ccd_out + ((long)wid * m.nxn_ccd + m.nxn_ccdid[q]) * CCD_OUT;
         if (lane < CCD_OUT) out[lane] = W[CL.out + lane];
         __syncthreads();
         continue;
       }
-      put_cgeom(W + CL.geoms, gx + 3 * g1, gm + 9 * g1, gsize + 3 * g1, t1, md1 >= 0 ? m.mesh_vertadr[md1] : 0, md1 >= 0 ? m.mesh_vertnum[md1] : 0,
-                md1);
-      put_cgeom(W + CL.geoms + CGEOM_WORDS, gx + 3 * g2, gm + 9 * g2, gsize + 3 * g2, t2, md2 >= 0 ? m.mesh_vertadr[md2] : 0,
-                md2 >= 0 ? m.mesh_vertnum[md2] : 0, md2);
+      put_pair_geoms(m, W, CL, gx, gm, gsize, g1, g2);
       __syncthreads();
-      const int pid = m.nxn_pairid[2 * q];  // explicit <pair>: its own margin (collision_core.py:271)
-      const int nc = ccd_pair(W, m.ccd_epa_iterations, MR(opt_ccd_tolerance)[0], m.opt_ccd_iterations,
-                              pid > -1 ? MR(pair_margin)[pid] : gmargin[g1] + gmargin[g2], mesh_vert, 0.0f, &MP,
-                              (m.opt_enableflags & ENBL_MULTICCD) != 0, m.nmaxpolygon, m.nmaxmeshdeg);
+      const int nc = ccd_pair_of(m, wid, W, pair_margin(m, wid, m.nxn_pairid[2 * q], g1, g2), 0.0f, MP);
       float* out = d.ccd_out + ((long)wid * m.nxn_ccd + m.nxn_ccdid[q]) * CCD_OUT;
       if (lane < CCD_OUT) out[lane] = ccd_record_word(lane, nc, W + CL.out);
       __syncthreads();

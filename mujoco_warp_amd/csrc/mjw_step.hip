@@ -506,7 +506,7 @@ __device__ __forceinline__ void camlight(const mjw_model_t& m, const mjw_data_t&
       rot_vec_quat(t, light_pos + 3 * l, xq);
       for (int i = 0; i < 3; i++) lx[i] = xp[i] + t[i];
       rot_vec_quat(ld, light_dir + 3 * l, xq);
-      norm = !(is_target && tgt < 0);  // smooth.py:732 returns before normalize
+      norm = !(is_target && tgt < 0);  // smooth.py:726-732 returns before normalize
     } else if (mode == CAM_TRACK) {
       for (int i = 0; i < 3; i++) { ld[i] = light_dir0[3 * l + i]; lx[i] = xp[i] + light_pos0[3 * l + i]; }
     } else if (mode == CAM_TRACKCOM) {
@@ -618,100 +618,8 @@ __device__ __forceinline__ float cholesky_solve(const float* Lm, int n, int nvs,
   }
   return lane < n ? y : 0.0f;
 }
-// collision primitives, AABB/OBB filters and contact_params: mjw_narrow.h
-
-// collision_driver.py:274-321; gxpos / gxmat: the world's geom frames (LDS in the fused kernels, HBM in the
-// stand-alone broadphase entry point)
-__device__ __forceinline__ bool broadphase_filter_g(const mjw_model_t& m, const float* gxpos, const float* gxmat, int wid, int g1, int g2) {
-  const float* geom_aabb = MR(geom_aabb);
-  const float* geom_rbound = MR(geom_rbound);
-  const float* geom_margin = MR(geom_margin);
-  float rb1 = geom_rbound[g1], rb2 = geom_rbound[g2];
-  float mg1 = geom_margin[g1], mg2 = geom_margin[g2];
-  const float* xp1 = gxpos + 3 * g1;
-  const float* xp2 = gxpos + 3 * g2;
-  const float* xm1 = gxmat + 9 * g1;
-  const float* xm2 = gxmat + 9 * g2;
-  int filt = m.opt_broadphase_filter;
-  if (rb1 == 0.0f || rb2 == 0.0f) {
-    if (filt & FILTER_PLANE) {
-      if (rb1 == 0.0f) {
-        float dif[3] = {xp2[0] - xp1[0], xp2[1] - xp1[1], xp2[2] - xp1[2]}, n[3] = {xm1[2], xm1[5], xm1[8]};
-        return dot3(dif, n) <= rb2 + mg1 + mg2;
-      } else {
-        float dif[3] = {xp1[0] - xp2[0], xp1[1] - xp2[1], xp1[2] - xp2[2]}, n[3] = {xm2[2], xm2[5], xm2[8]};
-        return dot3(dif, n) <= rb1 + mg1 + mg2;
-      }
-    }
-    return true;
-  }
-  if (filt & FILTER_SPHERE) {
-    float bound = rb1 + rb2 + mg1 + mg2;
-    float dif[3] = {xp2[0] - xp1[0], xp2[1] - xp1[1], xp2[2] - xp1[2]};
-    if (!(dot3(dif, dif) <= bound * bound)) return false;
-  }
-  if (filt & FILTER_AABB)
-    if (!aabb_filter(geom_aabb + 6 * g1, geom_aabb + 6 * g2, geom_aabb + 6 * g1 + 3, geom_aabb + 6 * g2 + 3, mg1 + mg2, xp1, xp2, xm1, xm2))
-      return false;
-  if (filt & FILTER_OBB)
-    if (!obb_filter(geom_aabb + 6 * g1, geom_aabb + 6 * g2, geom_aabb + 6 * g1 + 3, geom_aabb + 6 * g2 + 3, mg1 + mg2, xp1, xp2, xm1, xm2))
-      return false;
-  return true;
-}
-__device__ __forceinline__ bool broadphase_filter(const mjw_model_t& m, const Lay& L, const float* s, int wid, int g1, int g2) {
-  return broadphase_filter_g(m, s + L.gxpos, s + L.gxmat, wid, g1, g2);
-}
-
-// narrowphase of one pair (collision_primitive.py:280-662); pair is type-sorted on the host
-// BOX = false compiles out the pairs with a box (sphere-box, capsule-box; plane-box and box-box are
-// handled by the caller): models without boxes then run a kernel with 118 instead of 128+ VGPRs and
-// no scratch spills
-template <bool BOX>
-__device__ __forceinline__ void narrowphase_g(const mjw_model_t& m, const float* gxpos, const float* gxmat, int wid, int g1, int g2, float margin,
-                                              Con2& c) {
-  const float* geom_size = MR(geom_size);
-  int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
-  const float* p1 = gxpos + 3 * g1;
-  const float* p2 = gxpos + 3 * g2;
-  const float* r1 = gxmat + 9 * g1;
-  const float* r2 = gxmat + 9 * g2;
-  const float* s1 = geom_size + 3 * g1;
-  const float* s2 = geom_size + 3 * g2;
-  float n1[3] = {r1[2], r1[5], r1[8]}, n2[3] = {r2[2], r2[5], r2[8]};
-  c.n = 0;
-  if (t1 == GEOM_PLANE && t2 == GEOM_SPHERE) {
-    c.dist[0] = plane_sphere(c.pos[0], n1, p1, p2, s2[0]);
-    make_frame(c.frame[0], n1);
-    c.n = 1;
-  } else if (t1 == GEOM_PLANE && t2 == GEOM_CAPSULE) {
-    plane_capsule(c, n1, p1, p2, n2, s2[0], s2[1]);
-  } else if (t1 == GEOM_SPHERE && t2 == GEOM_SPHERE) {
-    float nrm[3];
-    c.dist[0] = sphere_sphere(c.pos[0], nrm, p1, s1[0], p2, s2[0]);
-    make_frame(c.frame[0], nrm);
-    c.n = 1;
-  } else if (t1 == GEOM_SPHERE && t2 == GEOM_CAPSULE) {
-    float a[3], b[3], pt[3], nrm[3];
-    for (int i = 0; i < 3; i++) { a[i] = p2[i] - n2[i] * s2[1]; b[i] = p2[i] + n2[i] * s2[1]; }
-    closest_segment_point(pt, a, b, p1);
-    c.dist[0] = sphere_sphere(c.pos[0], nrm, p1, s1[0], pt, s2[0]);
-    make_frame(c.frame[0], nrm);
-    c.n = 1;
-  } else if (t1 == GEOM_CAPSULE && t2 == GEOM_CAPSULE) {
-    capsule_capsule(c, p1, n1, s1[0], s1[1], p2, n2, s2[0], s2[1], margin);
-  } else if (BOX && t1 == GEOM_SPHERE && t2 == GEOM_BOX) {  // collision_primitive.py:1047-1114
-    float nrm[3];
-    c.dist[0] = sphere_box(c.pos[0], nrm, p1, s1[0], p2, r2, s2);
-    make_frame(c.frame[0], nrm);
-    c.n = 1;
-  } else if (BOX && t1 == GEOM_CAPSULE && t2 == GEOM_BOX) {  // collision_primitive.py:1117-1199
-    capsule_box(c, p1, n1, s1[0], s1[1], p2, r2, s2);
-  }
-}
-template <bool BOX>
-__device__ __forceinline__ void narrowphase(const mjw_model_t& m, const Lay& L, const float* s, int wid, int g1, int g2, float margin, Con2& c) {
-  narrowphase_g<BOX>(m, s + L.gxpos, s + L.gxmat, wid, g1, g2, margin, c);
-}
+// collision primitives, AABB/OBB filters, contact_params and the per-pair functions broadphase_filter and
+// primitive_pair: mjw_narrow.h
 
 
 // -------------------------------------------------------------------------------------------
@@ -1198,7 +1106,7 @@ __device__ __forceinline__ void collision_and_constraints(const mjw_model_t& m, 
       bool pass = false;
       if (p < m.nxn) {
         int g1 = m.nxn_geom_pair[2 * p], g2 = m.nxn_geom_pair[2 * p + 1];
-        pass = m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, L, s, wid, g1, g2);
+        pass = m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, wid, s + L.gxpos, s + L.gxmat, g1, g2);
       }
       unsigned long long bal = __ballot(pass);
       int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
@@ -1284,7 +1192,7 @@ __device__ __forceinline__ void collision_and_constraints(const mjw_model_t& m, 
               if (dist < margin && pairid0 >= -1) bmask |= 1u << q;
             }
           } else {
-            narrowphase<BOX>(m, L, s, wid, g1, g2, margin, c);
+            primitive_pair<BOX>(m, wid, s + L.gxpos, s + L.gxmat, g1, g2, margin, c);
           }
         }
         // active contacts (write_contact collision_core.py:199-213); plane-box corners and pre-pass points
@@ -2996,7 +2904,7 @@ __device__ __forceinline__ void ccd_body(const mjw_model_t& m, const mjw_data_t&
     const int g1 = m.nxn_geom_pair[2 * p], g2 = m.nxn_geom_pair[2 * p + 1];
     const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
     if (!prepass_prim(t1, t2)) continue;
-    if (!(m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, L, s, wid, g1, g2))) continue;
+    if (!(m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, wid, s + L.gxpos, s + L.gxmat, g1, g2))) continue;
     const float *p1 = s + L.gxpos + 3 * g1, *p2 = s + L.gxpos + 3 * g2, *r1 = s + L.gxmat + 9 * g1, *r2 = s + L.gxmat + 9 * g2;
     const float *s1 = gsize + 3 * g1, *s2 = gsize + 3 * g2;
     const float n1[3] = {r1[2], r1[5], r1[8]}, n2[3] = {r2[2], r2[5], r2[8]};
@@ -3034,7 +2942,7 @@ __device__ __forceinline__ void ccd_body(const mjw_model_t& m, const mjw_data_t&
     const int g1 = m.nxn_geom_pair[2 * p], g2 = m.nxn_geom_pair[2 * p + 1];
     const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
     if (prepass_prim(t1, t2)) continue;
-    const bool pass = m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, L, s, wid, g1, g2);
+    const bool pass = m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, wid, s + L.gxpos, s + L.gxmat, g1, g2);
     int nc = 0;
     if (HF && pass && t1 == GEOM_HFIELD) {
       // heightfield-convex pair (collision_convex.py:158-697): its record is built whole in the workspace
@@ -3092,7 +3000,7 @@ __global__ void __launch_bounds__(256) nxn_broadphase_kernel(const mjw_model_t m
   const int g1 = m.nxn_geom_pair[2 * p], g2 = m.nxn_geom_pair[2 * p + 1];
   const float* gx = d.geom_xpos + (long)wid * m.ngeom * 3;
   const float* gm = d.geom_xmat + (long)wid * m.ngeom * 9;
-  if (!(m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter_g(m, gx, gm, wid, g1, g2))) return;
+  if (!(m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, wid, gx, gm, g1, g2))) return;
   const int k = atomicAdd(d.ncollision, 1);
   if (k >= d.naconmax) return;
   cpair[2 * k] = g1;
@@ -3193,7 +3101,7 @@ __global__ void __launch_bounds__(256) sap_broadphase_kernel(const mjw_model_t m
         else pb = mid;
       }
       if (p < 0) continue;
-      if (!(m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter_g(m, gx, gm, wid, ga, gb))) continue;
+      if (!(m.nxn_pairid[2 * p + 1] >= 0 || broadphase_filter(m, wid, gx, gm, ga, gb))) continue;
       const int k = atomicAdd(d.ncollision, 1);
       if (k >= d.naconmax) continue;
       cpair[2 * k] = m.nxn_geom_pair[2 * p];
@@ -3276,7 +3184,7 @@ __global__ void __launch_bounds__(256) primitive_narrowphase_kernel(const mjw_mo
     for (int q = 0; q < n; q++) write(q, dist[q], pos[q], frame);
   } else {
     Con2 c;
-    narrowphase_g<true>(m, gx, gm, wid, g1, g2, margin, c);
+    primitive_pair<true>(m, wid, gx, gm, g1, g2, margin, c);
     for (int q = 0; q < c.n; q++) write(q, c.dist[q], c.pos[q], c.frame[q]);
   }
 }
