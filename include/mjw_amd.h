@@ -19,7 +19,8 @@
  *   mjw_sensor            <- sensor.sensor_pos/_vel/_acc  sensor.py:761,1377,2447
  *   mjw_ctrl_noise        <- benchmark.ctrl_noise         _src/benchmark.py:41-83
  *   mjw_rays              <- ray.rays (no render context) ray.py:1212-1312
- *   mjw_render            <- render.render (brute force over the geoms, no BVH; no textures, no flex) render.py:515-830
+ *   mjw_render            <- render.render (brute force over the geoms; no textures, no flex) render.py:515-830
+ *   mjw_rays_bvh / mjw_render_bvh <- the same with a static BVH per mesh (no BVH over the geoms, none to refit)
  *   mjw_inverse           <- inverse.inverse's constraint + combine  inverse.py, solver.py init_context(grad=False)
  *
  * Ownership: the caller owns every buffer (device pointers below); the library
@@ -269,6 +270,25 @@ typedef struct mjw_render_t {
   int64_t rgb_ld, depth_ld, seg_ld; /* row lengths; the kernel writes no pixel at or past them */
 } mjw_render_t;
 
+/* The static mesh BVHs of a render context (mjw_rays_bvh, mjw_render_bvh): one binary tree per mesh, in the mesh's
+ * frame, built on the host from the unbatched mesh_vert.  Every pointer is a device pointer.
+ * node: 8 words per node, the box minimum (3 floats), the box maximum (3 floats) and two int32: an inner node holds
+ * the left child and (right child | split axis << 29), children counted from the mesh's first node and always
+ * greater than their parent; a leaf (second int <= 0) holds its first entry of tri, counted from the mesh's first
+ * entry, and minus its number of triangles (at most leaf_size).  tri: face ids local to the mesh, grouped by leaf.
+ * adr: per mesh its first node, its number of nodes, its first entry of tri (= mesh_faceadr) and its depth. */
+typedef struct mjw_bvh_t {
+  int32_t nmesh;      /* must equal mjw_model_t.nmesh */
+  int32_t nnode;      /* nodes of all meshes */
+  int32_t ntri;       /* entries of tri; must equal mjw_ray_model_t.nmeshface */
+  int32_t leaf_size;  /* triangles per leaf at the most; at most 4 */
+  int32_t max_depth;  /* levels of the deepest tree; at most 32 */
+  int32_t min_faces;  /* meshes with fewer faces are intersected by the loop over their faces (same results) */
+  const float* node;   /* (nnode, 8) */
+  const int32_t* tri;  /* (ntri,) */
+  const int32_t* adr;  /* (nmesh, 4) */
+} mjw_bvh_t;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -396,6 +416,16 @@ int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* r
  * A successful no-op for d->nworld <= 0 or rc->ntile == 0; null arguments give -1, a ray model whose ngeom differs
  * -4, more workgroups than the grid holds -2. */
 int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, void* stream);
+
+/* mjw_rays / mjw_render with the meshes walked through the BVHs of `bvh` in place of the loop over every face; the
+ * results are those of mjw_rays / mjw_render.  The trees were built from the unbatched mesh_vert: with a per-world
+ * mesh_vert (mesh_vert_nb > 1), and for a model without mesh faces, the call is mjw_rays / mjw_render.  A null bvh
+ * or null tables give -1; counts that differ from the model's, a leaf_size above 4 or a max_depth above 32 give -4. */
+int mjw_rays_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb, const float* vec,
+                 int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude, float* dist, int* geomid,
+                 float* normal, const mjw_bvh_t* bvh, void* stream);
+int mjw_render_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
+                   void* stream);
 
 /* Inverse dynamics at the caller's acceleration (inverse.py `inverse`, its constraint and combine steps; ABI 36):
  * with the position and velocity stages of the current state in `d` (qM, qfrc_bias, qfrc_passive and the constraint

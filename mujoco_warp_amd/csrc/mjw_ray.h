@@ -389,6 +389,31 @@ inline void fill_geom_args(GeomArgs& a, const mjw_model_t* m, const mjw_data_t* 
   a.hfield_nrow = m->hfield_nrow; a.hfield_ncol = m->hfield_ncol; a.hfield_adr = m->hfield_adr;
 }
 
+// the mesh BVHs of a render context (mjw_bvh_t; bvh.py has the layout).  A block of its own, handed only to the
+// kernels built with BVH = true, so that GeomArgs and the kernels without a BVH stay as they are.
+struct BvhArgs {
+  int nnode, ntri, nmesh, min_faces;  // min_faces: meshes with fewer faces keep the face loop
+  const float* node;  // (nnode, 8): box min 3, box max 3, two ints
+  const int* tri;     // (ntri,) face ids local to the mesh, grouped by leaf
+  const int* adr;     // (nmesh, 4): first node, nodes, first tri, depth
+};
+constexpr int BVH_LEAF = 4;     // triangles per leaf at the most (bvh.py BVH_LEAF)
+constexpr int BVH_STACK = 64;   // traversal stack entries: one per lane of a VGPR; the trees have at most 32 levels
+constexpr int BVH_AXIS_SHIFT = 29;
+
+// host: whether a call with this bvh walks the trees (1), runs the face loop (0), or is refused (< 0)
+inline int check_bvh_args(const char* who, const mjw_model_t* m, const mjw_ray_model_t* rm, const mjw_bvh_t* bvh, BvhArgs& bv) {
+  const std::string w(who);
+  if (!bvh) return set_last_error(-1, (w + ": null bvh").c_str());
+  if (bvh->nmesh != m->nmesh || bvh->ntri != rm->nmeshface) return set_last_error(-4, (w + ": the bvh was built for another model (nmesh / nmeshface)").c_str());
+  if (bvh->nnode < 0 || bvh->leaf_size > BVH_LEAF || bvh->max_depth > 32) return set_last_error(-4, (w + ": bvh nnode / leaf_size / max_depth out of range").c_str());
+  if (rm->nmeshface <= 0 || m->nmesh <= 0 || bvh->nnode == 0 || m->mesh_vert_nb > 1) return 0;
+  if (!bvh->node || !bvh->tri || !bvh->adr) return set_last_error(-1, (w + ": null bvh table").c_str());
+  bv.nnode = bvh->nnode; bv.ntri = bvh->ntri; bv.nmesh = bvh->nmesh; bv.min_faces = bvh->min_faces;
+  bv.node = bvh->node; bv.tri = bvh->tri; bv.adr = bvh->adr;
+  return 1;
+}
+
 __device__ __forceinline__ const float* row(const float* p, int nb, long cnt, int w) { return nb <= 1 ? p : p + (long)(w % nb) * cnt; }
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
@@ -432,13 +457,123 @@ __device__ __forceinline__ void stage_chunk(const GeomArgs& a, int wid, int g0, 
   }
 }
 
+// The mesh's BVH walked by the whole wave in place of the face loop; the result is bitwise the face loop's (the
+// nearest triangle of the mesh, the lowest face id among equal distances: x, nl).
+//
+// The walk is wave-uniform: one node at a time, read through uniform addresses, and one traversal stack for the wave
+// kept in a VGPR (entry i in lane i: a push is a select on the lane id, a pop a v_readlane at a uniform index).  A node
+// is entered when any candidate lane's ray meets its box no farther than that lane's limit: its nearest triangle of
+// this mesh so far, or `best`, the nearest geom so far, beyond which a hit is dropped anyway.  An inner node sends
+// the walk to the child on the side the first such lane's ray comes from and pushes the other.
+//
+// The slab test is conservative with respect to ray_triangle.  That routine accepts a ray that passes a triangle
+// within rounding, a few ulp of the distance D between the ray's origin and the triangle; the box is grown by
+// 1e-5 (|lp|_1 + the root box's largest coordinates), more than ten times that, on every side.  A direction
+// component of (relative) size under 1e-12 is treated as zero: that axis then only asks whether the origin lies in
+// the grown slab, and no 0 * inf is formed.  The entry distance is compared after a cut of 2^-10: ray_triangle's
+// distance carries a relative error of about 1e-7 / sin(grazing angle), so the comparison stays on the safe side
+// down to grazing angles of 1e-4 rad.  ANYHIT: a lane leaves the walk at its first hit under `best`.
+template <bool ANYHIT>
+__device__ __forceinline__ float mesh_bvh(const BvhArgs& bv, int mesh, const float* vert, const int* face, int nface, bool cand,
+                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl) {
+  float x = -1.0f;
+  if (mesh >= bv.nmesh) return x;  // (uniform, like every test of the tables below: a table that does not fit hits nothing)
+  const int* adr = bv.adr + 4 * (long)mesh;
+  const int nadr = uni(adr[0]), nnode = uni(adr[1]), triadr = uni(adr[2]);
+  if (nadr < 0 || nnode < 1 || nadr > bv.nnode - nnode || triadr < 0 || triadr > bv.ntri - nface) return x;  // (uniform)
+  const float* nodes = bv.node + 8 * (long)nadr;
+  const int* tri = bv.tri + triadr;
+
+  const float vmax = fmaxf(fabsf(lv[0]), fmaxf(fabsf(lv[1]), fabsf(lv[2])));
+  float inv[3];
+  bool par[3];
+  for (int i = 0; i < 3; i++) {
+    par[i] = !(fabsf(lv[i]) > 1e-12f * vmax);
+    inv[i] = par[i] ? 0.0f : 1.0f / lv[i];
+  }
+  float pad = fabsf(lp[0]) + fabsf(lp[1]) + fabsf(lp[2]);
+  for (int i = 0; i < 3; i++) pad += fmaxf(fabsf(nodes[i]), fabsf(nodes[3 + i]));
+  pad = pad * 1e-5f + 1e-30f;
+
+  int bf = 0x7fffffff;  // the face of x
+  const int lane = (int)(threadIdx.x & 63u);
+  int stack = 0, sp = 0, node = 0;
+  for (;;) {
+    const float* nd = nodes + 8 * node;
+    const int ia = uni(reinterpret_cast<const int*>(nd)[6]), ib = uni(reinterpret_cast<const int*>(nd)[7]);
+    float tmin = 0.0f, tmax = MJW_MAXVAL;
+    for (int i = 0; i < 3; i++) {
+      const float a = nd[i] - pad - lp[i], b = nd[3 + i] + pad - lp[i];  // a <= 0 <= b: the origin is in the slab
+      float t0, t1;
+      if (par[i]) {
+        const bool in = a <= 0.0f && b >= 0.0f;
+        t0 = in ? -MJW_MAXVAL : MJW_MAXVAL;
+        t1 = in ? MJW_MAXVAL : -MJW_MAXVAL;
+      } else {
+        t0 = fminf(a * inv[i], b * inv[i]);
+        t1 = fmaxf(a * inv[i], b * inv[i]);
+      }
+      tmin = fmaxf(tmin, t0);
+      tmax = fminf(tmax, t1);
+    }
+    const float lim = x >= 0.0f ? fminf(x, best) : best;
+    const bool go = cand && tmin <= tmax && tmin * 0.9990234375f <= lim;
+    const unsigned long long mask = __ballot(go);
+    if (mask) {
+      if (ib <= 0) {  // a leaf: its triangles, by their original face ids
+        const int cnt = min(-ib, BVH_LEAF);
+        if (ia >= 0 && ia <= nface - cnt) {
+          for (int i = 0; i < cnt; i++) {
+            const int f = uni(tri[ia + i]);
+            if ((unsigned)f >= (unsigned)nface) continue;
+            const int* idx = face + 3 * (long)f;
+            float n[3];
+            const float sol = ray_triangle(vert + 3 * idx[0], vert + 3 * idx[1], vert + 3 * idx[2], lp, lv, b0, b1, n);
+            if (sol >= 0.0f && (x < 0.0f || sol < x || (sol == x && f < bf))) {
+              x = sol;
+              bf = f;
+              nl[0] = n[0]; nl[1] = n[1]; nl[2] = n[2];
+            }
+          }
+          if (ANYHIT) cand = cand && !(x >= 0.0f && x < best);
+        }
+      } else {
+        const int axis = ib >> BVH_AXIS_SHIFT;
+        int l = ia, r = ib & ((1 << BVH_AXIS_SHIFT) - 1);
+        // children lie after their parent, so a walk over any table ends
+        if (l > node && l < nnode && r > node && r < nnode) {
+          const float dsel = axis == 0 ? lv[0] : (axis == 1 ? lv[1] : lv[2]);
+          const int first = uni((int)__ffsll((long long)mask) - 1);
+          const float dv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dsel), first));
+          if (dv < 0.0f) {
+            const int t = l;
+            l = r;
+            r = t;
+          }
+          if (sp < BVH_STACK) {  // (never full: at most one entry per level)
+            stack = lane == sp ? r : stack;
+            sp++;
+          }
+          node = l;
+          continue;
+        }
+      }
+    }
+    if (sp == 0) break;
+    sp--;
+    node = uni(__builtin_amdgcn_readlane(stack, sp));
+  }
+  return x;
+}
+
 // Every lane's ray (pnt, vec; world frame) against the n staged geoms g0 ..: a hit nearer than `best` (strict
 // `<`, so equal distances stay with the lowest geom id) replaces best / bid / bn (world-frame normal).  Lanes
 // with !active, and geoms of body excl, are left alone.  ANYHIT: a lane that has a hit (bid >= 0) stops looking,
 // so with best preset to a distance limit the result says only whether anything lies nearer than the limit.
-template <bool ANYHIT>
-__device__ __forceinline__ void trace_chunk(const GeomArgs& a, int wid, const float* recs, int g0, int n, bool active, int excl,
-                                            const float* pnt, const float* vec, float& best, int& bid, float* bn) {
+// BVH: meshes of at least bv.min_faces faces are walked through their BVH (bv) in place of the face loop.
+template <bool ANYHIT, bool BVH>
+__device__ __forceinline__ void trace_chunk(const GeomArgs& a, const BvhArgs& bv, int wid, const float* recs, int g0, int n, bool active,
+                                            int excl, const float* pnt, const float* vec, float& best, int& bid, float* bn) {
   for (int k = 0; k < n; k++) {
     const float* rec = recs + k * RECW;
     const int* ri = reinterpret_cast<const int*>(rec);
@@ -464,13 +599,18 @@ __device__ __forceinline__ void trace_chunk(const GeomArgs& a, int wid, const fl
       // the face loop is wave-uniform: indices and vertices are read through uniform addresses
       const float* vert = row(a.mesh_vert, a.vert_nb, (long)a.nmeshvert * 3, wid) + 3 * (long)a.mesh_vertadr[mesh];
       const int f0 = a.mesh_faceadr[mesh], f1 = min(f0 + a.mesh_facenum[mesh], a.nmeshface);
-      for (int f = f0; f < f1; f++) {
-        const int* idx = a.mesh_face + 3 * (long)f;
-        float n[3];
-        const float sol = ray_triangle(vert + 3 * idx[0], vert + 3 * idx[1], vert + 3 * idx[2], lp, lv, b0, b1, n);
-        if (sol >= 0.0f && (x < 0.0f || sol < x)) {
-          x = sol;
-          nl[0] = n[0]; nl[1] = n[1]; nl[2] = n[2];
+      if (BVH && f1 - f0 >= bv.min_faces) {  // (uniform)
+        if (f0 < 0 || f1 < f0) continue;
+        x = mesh_bvh<ANYHIT>(bv, mesh, vert, a.mesh_face + 3 * (long)f0, f1 - f0, cand, lp, lv, b0, b1, best, nl);
+      } else {
+        for (int f = f0; f < f1; f++) {
+          const int* idx = a.mesh_face + 3 * (long)f;
+          float n[3];
+          const float sol = ray_triangle(vert + 3 * idx[0], vert + 3 * idx[1], vert + 3 * idx[2], lp, lv, b0, b1, n);
+          if (sol >= 0.0f && (x < 0.0f || sol < x)) {
+            x = sol;
+            nl[0] = n[0]; nl[1] = n[1]; nl[2] = n[2];
+          }
         }
       }
     } else if (type == RG_HFIELD) {
@@ -493,9 +633,9 @@ __device__ __forceinline__ void trace_chunk(const GeomArgs& a, int wid, const fl
 // The whole loop: every chunk of world wid staged in `recs` (RAY_CHUNK * RECW floats of LDS) and traced.  Every
 // thread of the workgroup must call it (it holds barriers); a wave without an active lane skips the tracing.
 // staged: the model fits one chunk and an earlier call of this workgroup left it in `recs`.
-template <int NT, bool ANYHIT>
-__device__ __forceinline__ void geom_loop(const GeomArgs& a, int wid, float* recs, bool staged, bool active, int excl, const float* pnt,
-                                          const float* vec, float& best, int& bid, float* bn) {
+template <int NT, bool ANYHIT, bool BVH>
+__device__ __forceinline__ void geom_loop(const GeomArgs& a, const BvhArgs& bv, int wid, float* recs, bool staged, bool active, int excl,
+                                          const float* pnt, const float* vec, float& best, int& bid, float* bn) {
   for (int g0 = 0; g0 < a.ngeom; g0 += RAY_CHUNK) {
     const int n = min(RAY_CHUNK, a.ngeom - g0);
     if (!staged) {
@@ -503,7 +643,7 @@ __device__ __forceinline__ void geom_loop(const GeomArgs& a, int wid, float* rec
       stage_chunk<NT>(a, wid, g0, n, recs);
       __syncthreads();
     }
-    if (__any(active)) trace_chunk<ANYHIT>(a, wid, recs, g0, n, active, excl, pnt, vec, best, bid, bn);
+    if (__any(active)) trace_chunk<ANYHIT, BVH>(a, bv, wid, recs, g0, n, active, excl, pnt, vec, best, bid, bn);
   }
 }
 

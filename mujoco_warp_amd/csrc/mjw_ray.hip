@@ -9,7 +9,8 @@
 // worked out once per workgroup while staging, the inner loop tests only the flag and the ray's bodyexclude.
 // A geom no lane's bounding test passes is skipped by the whole wave (ballot), so the mesh and heightfield
 // loops run only in waves with a candidate ray.  The loop itself (staging, culling, nearest hit) is geom_loop
-// of mjw_ray.h, which the render kernel (mjw_render.hip) calls too.
+// of mjw_ray.h, which the render kernel (mjw_render.hip) calls too.  mjw_rays_bvh launches the same body built with
+// BVH = true (rays_bvh_kernel): meshes are walked through the static trees of a render context (mesh_bvh, mjw_ray.h).
 #include "mjw_common.h"
 #include "mjw_ray.h"
 
@@ -27,9 +28,8 @@ struct RayArgs {
   float* normal;
 };
 
-template <int NT>
-__global__ void __launch_bounds__(NT) rays_kernel(const RayArgs a) {
-  __shared__ float recs[RAY_CHUNK * RECW];
+template <int NT, bool BVH>
+__device__ __forceinline__ void rays_body(const RayArgs& a, const BvhArgs& bv, float* recs) {
   const int tid = threadIdx.x;
   const int wid = blockIdx.x / a.ntile, tile = blockIdx.x - wid * a.ntile;
   const int r = tile * NT + tid;
@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(NT) rays_kernel(const RayArgs a) {
 
   float best = MJW_MAXVAL, bn[3] = {0.0f, 0.0f, 0.0f};
   int bid = -1;
-  geom_loop<NT, false>(a.g, wid, recs, false, active, excl, pnt, vec, best, bid, bn);
+  geom_loop<NT, false, BVH>(a.g, bv, wid, recs, false, active, excl, pnt, vec, best, bid, bn);
 
   if (active) {
     const long o = (long)wid * a.nray + r;
@@ -53,20 +53,38 @@ __global__ void __launch_bounds__(NT) rays_kernel(const RayArgs a) {
   }
 }
 
+template <int NT>
+__global__ void __launch_bounds__(NT) rays_kernel(const RayArgs a) {
+  __shared__ float recs[RAY_CHUNK * RECW];
+  rays_body<NT, false>(a, BvhArgs{}, recs);
+}
+
+// the same with the meshes walked through the BVHs of a render context
+template <int NT>
+__global__ void __launch_bounds__(NT) rays_bvh_kernel(const RayArgs a, const BvhArgs bv) {
+  __shared__ float recs[RAY_CHUNK * RECW];
+  rays_body<NT, true>(a, bv, recs);
+}
+
 }  // namespace ray
 }  // namespace mjw
 
-extern "C" int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb,
-                        const float* vec, int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude,
-                        float* dist, int* geomid, float* normal, void* stream) {
+static int rays_launch(const char* who, const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb,
+                       const float* vec, int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude, float* dist,
+                       int* geomid, float* normal, const mjw_bvh_t* bvh, bool with_bvh, void* stream) {
   using namespace mjw::ray;
-  if (!m || !d || !rm) return mjw::set_last_error(-1, "mjw_rays: null model / data / ray model");
-  if (nray < 0) return mjw::set_last_error(-4, "mjw_rays: nray < 0");
+  const std::string w(who);
+  if (!m || !d || !rm) return mjw::set_last_error(-1, (w + ": null model / data / ray model").c_str());
+  if (nray < 0) return mjw::set_last_error(-4, (w + ": nray < 0").c_str());
+  BvhArgs bv;
+  memset(&bv, 0, sizeof(bv));
+  int walk = 0;
+  if (with_bvh && (walk = check_bvh_args(who, m, rm, bvh, bv)) < 0) return walk;
   if (nray == 0 || d->nworld <= 0) return 0;
-  if (!pnt || !vec || !bodyexclude || !dist || !geomid || !normal) return mjw::set_last_error(-1, "mjw_rays: null ray / output array");
+  if (!pnt || !vec || !bodyexclude || !dist || !geomid || !normal) return mjw::set_last_error(-1, (w + ": null ray / output array").c_str());
   if ((pnt_nb != 1 && pnt_nb != d->nworld) || (vec_nb != 1 && vec_nb != d->nworld))
-    return mjw::set_last_error(-4, "mjw_rays: pnt / vec batch must be 1 or nworld");
-  if (int e = check_geom_args("mjw_rays", m, d, rm)) return e;
+    return mjw::set_last_error(-4, (w + ": pnt / vec batch must be 1 or nworld").c_str());
+  if (int e = check_geom_args(who, m, d, rm)) return e;
 
   RayArgs a;
   memset(&a, 0, sizeof(a));
@@ -89,12 +107,32 @@ extern "C" int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray
   const int nt = nray <= 64 ? 64 : 256;
   a.ntile = (nray + nt - 1) / nt;
   const long nblock = (long)a.nworld * a.ntile;
-  if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, "mjw_rays: nworld x ray tiles exceeds the grid limit");
-  if (nt == 64)
+  if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, (w + ": nworld x ray tiles exceeds the grid limit").c_str());
+  if (walk) {
+    if (nt == 64)
+      hipLaunchKernelGGL(rays_bvh_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a, bv);
+    else
+      hipLaunchKernelGGL(rays_bvh_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a, bv);
+  } else if (nt == 64) {
     hipLaunchKernelGGL(rays_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a);
-  else
+  } else {
     hipLaunchKernelGGL(rays_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mjw::set_last_error((int)e, hipGetErrorString(e));
   return 0;
+}
+
+extern "C" int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb,
+                        const float* vec, int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude,
+                        float* dist, int* geomid, float* normal, void* stream) {
+  return rays_launch("mjw_rays", m, d, rm, pnt, pnt_nb, vec, vec_nb, nray, geomgroup, flg_static, bodyexclude, dist, geomid, normal, nullptr,
+                     false, stream);
+}
+
+extern "C" int mjw_rays_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb,
+                            const float* vec, int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude,
+                            float* dist, int* geomid, float* normal, const mjw_bvh_t* bvh, void* stream) {
+  return rays_launch("mjw_rays_bvh", m, d, rm, pnt, pnt_nb, vec, vec_nb, nray, geomgroup, flg_static, bodyexclude, dist, geomid, normal, bvh,
+                     true, stream);
 }

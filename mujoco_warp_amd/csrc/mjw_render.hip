@@ -64,9 +64,8 @@ __device__ __forceinline__ void pixel_ray(float fovy, const float* sensorsize, c
   normalize3(local);
 }
 
-template <int NT>
-__global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
-  __shared__ float recs[RAY_CHUNK * RECW];
+template <int NT, bool BVH>
+__device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& bv, float* recs) {
   const int tid = threadIdx.x;
   const int wid = blockIdx.x / a.ntile, t = blockIdx.x - wid * a.ntile;
   const int ci = a.tile[4 * t], x0 = a.tile[4 * t + 1], y0 = a.tile[4 * t + 2];
@@ -99,7 +98,7 @@ __global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
 
   float best = MJW_MAXVAL, bn[3] = {0.0f, 0.0f, 0.0f};
   int bid = -1;
-  geom_loop<NT, false>(a.g, wid, recs, false, active, -1, pnt, vec, best, bid, bn);
+  geom_loop<NT, false, BVH>(a.g, bv, wid, recs, false, active, -1, pnt, vec, best, bid, bn);
   const bool hit = bid >= 0;
 
   const long pix = (long)py * W + px;
@@ -153,7 +152,7 @@ __global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
       const float so[3] = {hp[0] + bn[0] * 1e-4f, hp[1] + bn[1] * 1e-4f, hp[2] + bn[2] * 1e-4f};
       float sbest = type == 1 ? 1e8f : r - 1e-3f, sn[3];
       int sid = -1;
-      geom_loop<NT, true>(a.g, wid, recs, a.g.ngeom <= RAY_CHUNK, active && ndotl > 0.0f, -1, so, L, sbest, sid, sn);
+      geom_loop<NT, true, BVH>(a.g, bv, wid, recs, a.g.ngeom <= RAY_CHUNK, active && ndotl > 0.0f, -1, so, L, sbest, sid, sn);
       if (sid >= 0) visible = 0.3f;
     }
     const float c = ndotl * att * visible;
@@ -171,12 +170,30 @@ __global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
   }
 }
 
+template <int NT>
+__global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
+  __shared__ float recs[RAY_CHUNK * RECW];
+  render_body<NT, false>(a, BvhArgs{}, recs);
+}
+
+// the same with the meshes walked through the BVHs of the render context
+template <int NT>
+__global__ void __launch_bounds__(NT) render_bvh_kernel(const RenderArgs a, const BvhArgs bv) {
+  __shared__ float recs[RAY_CHUNK * RECW];
+  render_body<NT, true>(a, bv, recs);
+}
+
 }  // namespace ray
 }  // namespace mjw
 
-extern "C" int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, void* stream) {
+static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
+                         bool with_bvh, void* stream) {
   using namespace mjw::ray;
   if (!m || !d || !rm || !rc) return mjw::set_last_error(-1, "mjw_render: null model / data / ray model / render context");
+  BvhArgs bv;
+  memset(&bv, 0, sizeof(bv));
+  int walk = 0;
+  if (with_bvh && (walk = check_bvh_args("mjw_render_bvh", m, rm, bvh, bv)) < 0) return walk;
   if (rc->ntile < 0 || rc->nrender < 0) return mjw::set_last_error(-4, "mjw_render: ntile / nrender < 0");
   if (rc->ntile == 0 || d->nworld <= 0) return 0;
   if (rc->tile_threads != 64 && rc->tile_threads != 256) return mjw::set_last_error(-4, "mjw_render: tile_threads must be 64 or 256");
@@ -211,11 +228,26 @@ extern "C" int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_r
   hipStream_t s = (hipStream_t)stream;
   const long nblock = (long)a.nworld * a.ntile;
   if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, "mjw_render: nworld x tiles exceeds the grid limit");
-  if (rc->tile_threads == 64)
+  if (walk) {
+    if (rc->tile_threads == 64)
+      hipLaunchKernelGGL(render_bvh_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a, bv);
+    else
+      hipLaunchKernelGGL(render_bvh_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a, bv);
+  } else if (rc->tile_threads == 64) {
     hipLaunchKernelGGL(render_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a);
-  else
+  } else {
     hipLaunchKernelGGL(render_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a);
+  }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mjw::set_last_error((int)e, hipGetErrorString(e));
   return 0;
+}
+
+extern "C" int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, void* stream) {
+  return render_launch(m, d, rm, rc, nullptr, false, stream);
+}
+
+extern "C" int mjw_render_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc,
+                              const mjw_bvh_t* bvh, void* stream) {
+  return render_launch(m, d, rm, rc, bvh, true, stream);
 }

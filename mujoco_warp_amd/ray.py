@@ -2,9 +2,12 @@
 
 One HIP launch (`mjw_rays`, csrc/mjw_ray.hip) on the Data's stream: for every world and ray the nearest geom
 along `pnt + x vec`, x >= 0, at the frames `d.geom_xpos` / `d.geom_xmat` the last position stage left (no
-kinematics run here, so it serves dense and sparse models alike).  There is no BVH in this build, so a render
-context (render.py) accelerates nothing here: `rc` other than None is refused, and flex elements are not hit
-(as on the reference's path without `rc`).  Meshes are brute force over their triangles.
+kinematics run here, so it serves dense and sparse models alike).  Without a render context meshes are brute
+force over their triangles.  With `rc`, a RenderContext of the same model and nworld (render.py), the launch is
+`mjw_rays_bvh`: every mesh is walked through the context's static BVH (bvh.py) with the same result bit for bit.
+The trees were built from the host model's vertices, so with a per-world batched `m.mesh_vert` (leading dim > 1)
+the call runs the face loop all the same.  Any other `rc` is refused.  Flex elements are not hit (as on the
+reference's path without `rc`).
 """
 
 from __future__ import annotations
@@ -71,9 +74,17 @@ def rays(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Opt
   bodyexclude: int32 (nray,), geoms of that body are skipped (-1: none).  Geoms with alpha 0 (their
   material's when they have one, else their own rgba) are skipped.  Outputs: dist float32 (nworld, nray),
   geomid int32 (nworld, nray), normal float32 (nworld, nray, 3); a miss gives -1, -1, 0, and equal distances
-  go to the lowest geom id."""
+  go to the lowest geom id.  rc: None, or a RenderContext made for this model and nworld, whose mesh BVHs then
+  replace the loop over every mesh face (same results); a context of another model or nworld raises ValueError."""
+  bvh = None
   if rc is not None:
-    raise NotImplementedError("rays: render contexts (BVH acceleration) are not part of this build; pass rc=None")
+    from .types import RenderContext
+
+    if not isinstance(rc, RenderContext):
+      raise NotImplementedError("rays: rc must be None or a RenderContext from create_render_context (its mesh BVHs are walked)")
+    from .render import _cbvh
+
+    bvh = _cbvh(rc, m, d, "rays")
   dev = d.qpos.device
   nworld = int(d.nworld)
   if not isinstance(pnt, torch.Tensor) or pnt.dim() != 3 or pnt.shape[2] != 3:
@@ -102,17 +113,23 @@ def rays(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Opt
   from .io import cdata, cmodel
 
   L = _lib.lib()
-  rcode = L.mjw_rays(cmodel(m), cdata(d), ctypes.byref(rm), pnt.data_ptr(), nb, vec.data_ptr(), int(vec.shape[0]), nray, group,
-                     int(bool(flg_static)), bodyexclude.data_ptr(), dist.data_ptr(), geomid.data_ptr(), normal.data_ptr(), _stream(d))
-  _lib.check(rcode, "mjw_rays")
+  args = (cmodel(m), cdata(d), ctypes.byref(rm), pnt.data_ptr(), nb, vec.data_ptr(), int(vec.shape[0]), nray, group,
+          int(bool(flg_static)), bodyexclude.data_ptr(), dist.data_ptr(), geomid.data_ptr(), normal.data_ptr())
+  if bvh is None:
+    _lib.check(L.mjw_rays(*args, _stream(d)), "mjw_rays")
+  else:
+    _lib.check(L.mjw_rays_bvh(*args, ctypes.byref(bvh), _stream(d)), "mjw_rays_bvh")
 
 
 def ray(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Optional[Sequence[int]] = None, flg_static: bool = True,
         bodyexclude: int = -1, rc=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
   """One ray per world (ray.py:1168-1209): pnt, vec of shape (nb, 1, 3) with nb = 1 (the same ray in every
-  world) or nworld.  Returns dist (nworld, 1), geomid (nworld, 1), normal (nworld, 1, 3)."""
+  world) or nworld.  Returns dist (nworld, 1), geomid (nworld, 1), normal (nworld, 1, 3).  rc: as for `rays`."""
   if rc is not None:
-    raise NotImplementedError("ray: render contexts (BVH acceleration) are not part of this build; pass rc=None")
+    from .types import RenderContext
+
+    if not isinstance(rc, RenderContext):
+      raise NotImplementedError("ray: rc must be None or a RenderContext from create_render_context (its mesh BVHs are walked)")
   if not isinstance(pnt, torch.Tensor) or pnt.dim() != 3 or pnt.shape[1] != 1:
     raise ValueError("ray: pnt must have shape (nb, 1, 3)")
   dev = d.qpos.device
@@ -121,5 +138,5 @@ def ray(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Opti
   dist = torch.empty((nworld, 1), dtype=torch.float32, device=dev)
   geomid = torch.empty((nworld, 1), dtype=torch.int32, device=dev)
   normal = torch.empty((nworld, 1, 3), dtype=torch.float32, device=dev)
-  rays(m, d, pnt, vec, geomgroup, flg_static, excl, dist, geomid, normal)
+  rays(m, d, pnt, vec, geomgroup, flg_static, excl, dist, geomid, normal, rc=rc)
   return dist, geomid, normal

@@ -1,11 +1,18 @@
 """Batched camera rendering: segmentation, depth and shaded RGB images of a model's cameras
 (mujoco_warp/_src/render.py `render`, io.py `create_render_context`, render_util.py readers).
 
-One HIP launch (`mjw_render`, csrc/mjw_render.hip) on the Data's stream per `render` call: a workgroup per
+One HIP launch (`mjw_render_bvh`, csrc/mjw_render.hip) on the Data's stream per `render` call: a workgroup per
 world, camera and 16 x 16 pixel tile makes the pixel rays from `d.cam_xpos` / `d.cam_xmat` and the per-world
 camera parameters, finds the nearest geom with the geom loop `rays` uses, and writes every pixel of every
-enabled output.  No kinematics run here: the frames are those the last position stage left.  This build has no
-BVH (`refit_bvh` does nothing), no textures, no flex rendering and no orthographic cameras.
+enabled output.  No kinematics run here: the frames are those the last position stage left.
+
+Meshes are intersected through a static BVH per mesh (bvh.py), built on the host when the context is made and
+walked by the kernel in place of the loop over every face, with the same result bit for bit (meshes of fewer than
+`rc.bvh_min_faces` faces, default bvh.BVH_MIN_FACES, keep the loop: the walk does not pay there).  The trees live
+in the mesh's own frame and meshes are rigid, so nothing is refit per step (`refit_bvh` does nothing).  They were
+built from the host model's vertices: when `m.mesh_vert` is batched per world (leading dim > 1) the call falls
+back to the face loop.  There is no BVH over the geoms (they are culled by bounding ball and box per wave) or over
+heightfields, no textures, no flex rendering and no orthographic cameras.
 """
 
 from __future__ import annotations
@@ -17,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .bvh import BVH_LEAF, BVH_MAX_DEPTH, BVH_MIN_FACES, NODE_WORDS, build_mesh_bvh
 from .types import Data, Model, RenderContext
 
 TILE = 16  # pixels per side of a workgroup's tile (csrc/mjw_render.hip)
@@ -41,7 +49,8 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
   `mjm.cam_resolution`.  render_rgb / render_depth / render_seg: a bool, a list with one bool per active camera,
   or None for the model's `cam_output` bits where the host model carries them, else RGB only.  A geom is drawn
   iff its group is one of enabled_geom_groups (each in 0..31).  cam_active: one bool per model camera (None: all).
-  use_shadows: lights with castshadow throw shadows.
+  use_shadows: lights with castshadow throw shadows.  The BVHs of the model's meshes are built here, on the host
+  (rc.mesh_bvh_node / mesh_bvh_tri / mesh_bvh_adr; empty for a model without meshes).
 
   Accepted and ignored: `use_textures` (the MJCF compiler keeps no textures, colours are mat_rgba / geom_rgba),
   `flex_render_smooth` (no flex rendering) and `use_precomputed_rays` (the rays are always made in the kernel, so
@@ -110,6 +119,11 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
 
   i32 = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a).astype(np.int32)), device=dev)
   nl = int(mjm.nlight)
+  nmesh, nmeshface = int(getattr(mjm, "nmesh", 0)), int(getattr(mjm, "nmeshface", 0))
+  if nmesh > 0:
+    node, tri, adr, bvh_depth = build_mesh_bvh(mjm.mesh_vert, mjm.mesh_vertadr, mjm.mesh_face, mjm.mesh_faceadr, mjm.mesh_facenum)
+  else:
+    node, tri, adr, bvh_depth = build_mesh_bvh(np.zeros((0, 3)), [], np.zeros((0, 3)), [], [])
   return RenderContext(
     nworld=nworld,
     nrender=ncam,
@@ -135,11 +149,19 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
     rgb_data=torch.zeros((nworld, ri), dtype=torch.int32, device=dev),
     depth_data=torch.zeros((nworld, di), dtype=torch.float32, device=dev),
     seg_data=torch.zeros((nworld, max(si, 1)), dtype=torch.int32, device=dev),
+    mesh_bvh_node=torch.as_tensor(node, device=dev),
+    mesh_bvh_tri=torch.as_tensor(tri, device=dev),
+    mesh_bvh_adr=torch.as_tensor(adr, device=dev),
+    bvh_leaf_size=BVH_LEAF,
+    bvh_max_depth=int(bvh_depth),
+    bvh_min_faces=BVH_MIN_FACES,
     # host copies for the readers and for validation
     _res=[(int(w), int(h)) for w, h in res],
     _adr=dict(rgb=[int(x) for x in rgb_adr], depth=[int(x) for x in depth_adr], seg=[int(x) for x in seg_adr]),
     _ncam_model=ncam_model,
     _nlight=nl,
+    _nmesh=nmesh,
+    _nmeshface=nmeshface,
   )
 
 
@@ -170,6 +192,32 @@ def _crender(rc: RenderContext) -> _lib.CRender:
   return c
 
 
+def _cbvh(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CBvh:
+  """mjw_bvh_t of the context's trees; ValueError when the context was made for another model or nworld."""
+  nmesh, nface = int(rc._nmesh), int(rc._nmeshface)
+  if nmesh != int(m.nmesh) or nface != int(m.nmeshface):
+    raise ValueError(f"{who}: the render context was made for a model with {nmesh} meshes and {nface} mesh faces, "
+                     f"this one has {m.nmesh} and {m.nmeshface}")
+  if int(rc.nworld) != int(d.nworld):
+    raise ValueError(f"{who}: the render context was made for nworld = {rc.nworld}, the Data has {d.nworld}")
+  dev = d.qpos.device
+  node, tri, adr = rc.mesh_bvh_node, rc.mesh_bvh_tri, rc.mesh_bvh_adr
+  for name, t, dtype, tail in (("mesh_bvh_node", node, torch.float32, (NODE_WORDS,)), ("mesh_bvh_tri", tri, torch.int32, ()),
+                               ("mesh_bvh_adr", adr, torch.int32, (4,))):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape[1:]) != tail:
+      raise ValueError(f"{who}: rc.{name} must be a contiguous {dtype} tensor of shape (n,{' %d' % tail[0] if tail else ''}) on {dev}")
+  if int(tri.shape[0]) != nface or int(adr.shape[0]) != nmesh:
+    raise ValueError(f"{who}: rc.mesh_bvh_tri / mesh_bvh_adr must hold {nface} faces and {nmesh} meshes")
+  if int(rc.bvh_leaf_size) > BVH_LEAF or int(rc.bvh_max_depth) > BVH_MAX_DEPTH:
+    raise ValueError(f"{who}: the context's BVH has leaves of {rc.bvh_leaf_size} triangles and {rc.bvh_max_depth} levels; "
+                     f"the kernel takes {BVH_LEAF} and {BVH_MAX_DEPTH}")
+  c = _lib.CBvh()
+  c.nmesh, c.nnode, c.ntri = nmesh, int(node.shape[0]), nface
+  c.leaf_size, c.max_depth, c.min_faces = int(rc.bvh_leaf_size), int(rc.bvh_max_depth), max(int(rc.bvh_min_faces), 0)
+  c.node, c.tri, c.adr = node.data_ptr(), tri.data_ptr(), adr.data_ptr()
+  return c
+
+
 def render(m: Model, d: Data, rc: RenderContext) -> None:
   """Renders every camera of the context in every world into rc.rgb_data / rc.depth_data / rc.seg_data
   (render.py:515-830), in one launch on the Data's stream; capturable in a graph.
@@ -180,7 +228,9 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   reference's cone), clamped and packed as a << 24 | r << 16 | g << 8 | b; background (25, 25, 51, 255).  A geom
   is drawn iff its group is enabled in the context: alpha plays no part.  cam_fovy, cam_intrinsic, geom_rgba
   and mat_rgba may be batched per world.  The camera, light and geom frames are those of the last position
-  stage (`forward`, `step`, `kinematics` + `camlight`)."""
+  stage (`forward`, `step`, `kinematics` + `camlight`).  Meshes are walked through the context's BVHs; with a
+  per-world batched `m.mesh_vert` (leading dim > 1), which the trees were not built from, the launch loops over
+  every face instead.  Both give the same images bit for bit."""
   if not isinstance(rc, RenderContext):
     raise ValueError("render: rc must be a RenderContext from create_render_context")
   dev = d.qpos.device
@@ -195,17 +245,19 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   from .io import cdata, cmodel
   from .ray import _ray_model
 
+  bvh = _cbvh(rc, m, d, "render")
   rm = _ray_model(m)
   c = _crender(rc)
   if c.ntile == 0:
     return
-  rcode = _lib.lib().mjw_render(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), _stream(d))
-  _lib.check(rcode, "mjw_render")
+  rcode = _lib.lib().mjw_render_bvh(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), _stream(d))
+  _lib.check(rcode, "mjw_render_bvh")
 
 
 def refit_bvh(m: Model, d: Data, rc: RenderContext) -> None:
-  """Does nothing: `render` walks the geoms directly and there is no BVH to refit.  It exists so that code
-  written for the reference (`refit_bvh` before every `render`) runs unchanged."""
+  """Does nothing.  The only BVHs are the per-mesh trees of the context, which live in each mesh's own frame:
+  meshes are rigid, so a moving geom moves its frame and the tree stays valid.  There is no BVH over the geoms to
+  refit.  It exists so that code written for the reference (`refit_bvh` before every `render`) runs unchanged."""
 
 
 def _view(rc, camera_index, which, out, shape_tail, dtype, name):

@@ -404,7 +404,12 @@ class RenderContext(_Container):
   light_type / light_active / light_castshadow (nlight,) int32: what `render` reads for the lights.  Buffers,
   in the reference's layouts: rgb_data (nworld, sum of rgb pixels) int32 holding a << 24 | r << 16 | g << 8 | b,
   depth_data (nworld, sum of depth pixels) float32, seg_data (nworld, max(sum of seg pixels, 1)) int32.
-  There is no BVH, no texture and no flex state."""
+  The static mesh BVHs (bvh.py has the layout; one tree per mesh, in the mesh's frame, built on the host from the
+  host model's mesh_vert): mesh_bvh_node (nnode, 8) float32, mesh_bvh_tri (nmeshface,) int32, mesh_bvh_adr
+  (nmesh, 4) int32, empty for a model without meshes; bvh_leaf_size and bvh_max_depth are host ints.  `render` and
+  `rays(rc=...)` walk them for the meshes of at least bvh_min_faces faces (a host int, default bvh.BVH_MIN_FACES; set
+  it to 0 to walk every mesh) and loop over the faces of the smaller ones, with the same results either way.
+  There is no BVH over the geoms, no texture and no flex state."""
 
 
 class Contact(_Container):
