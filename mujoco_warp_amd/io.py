@@ -121,6 +121,19 @@ _SPARSE_PAIRS = _PREPASS_PRIMITIVES
 _SPARSE_CCD_PAIRS = _CONVEX_TABLE
 
 
+SENSOR_LDS_WORDS = 16384  # 64 KB
+
+
+def sensor_lds_words(mjm) -> int:
+  """Words of LDS the sensor kernel's layout takes without the convex collision sensors' workspace (make_slayout,
+  csrc/mjw_sensor.hip): six per-body and four per-dof arrays, each rounded up to 4 words, and the tactile partner list."""
+  r4 = lambda n: (n + 3) & ~3  # noqa: E731
+  nb, nv = int(mjm.nbody), int(mjm.nv)
+  stypes = np.asarray(getattr(mjm, "sensor_type", np.zeros(0, dtype=np.int32)))
+  ntaxel = sum(int(mjm.mesh_vertnum[int(mjm.sensor_objid[s_])]) for s_ in np.nonzero(stypes == types.SensorType.TACTILE)[0])
+  return 4 * r4(6 * nb) + r4(10 * nb) + r4(3 * nb) + 2 * r4(6 * nv) + 2 * r4(nv) + (64 if ntaxel > 0 else 0)
+
+
 def put_model(mjm, device=None) -> types.Model:
   """Creates a model on device (reference io.py:77-647)."""
   dev = _device(device)
@@ -144,12 +157,14 @@ def put_model(mjm, device=None) -> types.Model:
   if unsupported:
     raise NotImplementedError(f"{EnableBit(unsupported).name} is unsupported.")
   sparse = is_sparse(mjm) or getattr(mjm, "nflex", 0) > 0
-  if sparse:
-    # the workgroup-per-world sparse / flex pipeline (csrc/mjw_sparse.hip) covers this subset
-    if getattr(mjm, "nsensor", 0):
-      # the sensor kernel (csrc/mjw_sensor.hip) stages a world's body / dof state in 64 KB of LDS
-      if 37 * mjm.nbody + 14 * mjm.nv > 16384:
-        raise NotImplementedError("sparse / flex models: sensors need 37 nbody + 14 nv <= 16384 in this build (the flex bodies exceed it).")
+  if getattr(mjm, "nsensor", 0):
+    # the sensor kernel (csrc/mjw_sensor.hip) stages a world's body / dof state in 64 KB of LDS, on the dense and on the
+    # sparse / flex path alike
+    words = sensor_lds_words(mjm)
+    if words > SENSOR_LDS_WORDS:
+      raise NotImplementedError(
+        f"sensors: the sensor kernel stages 37 words per body, 14 per dof and 64 for tactile sensors in {SENSOR_LDS_WORDS} words (64 KB) of LDS; "
+        f"nbody {mjm.nbody}, nv {mjm.nv} need {words}.  (The convex collision sensors' workspace is checked apart, and past it at launch.)")
   for st in np.unique(getattr(mjm, "sensor_type", np.zeros(0, dtype=np.int32))):
     if int(st) not in types.SUPPORTED_SENSORS:
       raise NotImplementedError(f"sensor type {int(st)} is not supported by this build yet.")

@@ -4047,6 +4047,13 @@ ORC_BATCH(orc_fwd_acceleration, fwd_acceleration)
 ORC_BATCH(orc_solve, solve)
 ORC_BATCH(orc_euler, integrate)
 
+/* forward.py:981-998, the acceleration stage alone: rne_postconstraint and the acceleration sensors from the Data's
+ * qacc and efc_force as they stand (a test writes another precision's solution there first) */
+static void sensor_acc_world(const orc_model* m, orc_data* d) {
+  if (m->nsensor > 0 && !(m->opt_disableflags & DSBL_SENSOR)) sensor_acc(m, d);
+}
+ORC_BATCH(orc_sensor_acc, sensor_acc_world)
+
 void orc_step(const orc_model* m, const orc_data* b, int nworld, int nthread) {
 #ifdef _OPENMP
 #pragma omp parallel for schedule(dynamic, 4) num_threads(nthread > 0 ? nthread : 1)

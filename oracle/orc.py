@@ -279,6 +279,10 @@ class OracleData:
   def euler(self):
     self._call("orc_euler")
 
+  def sensor_acc(self):
+    """rne_postconstraint and the acceleration sensors from the current qacc / efc_force."""
+    self._call("orc_sensor_acc")
+
   def ctrl_noise(self, step, center=None, std=0.01, rate=0.1, world_offset=0):
     om = self.om
     c = np.zeros(0, dtype=om.dtype) if center is None else np.ascontiguousarray(center, dtype=om.dtype)
