@@ -22,6 +22,7 @@
  *   mjw_render            <- render.render (brute force over the geoms; no textures, no flex) render.py:515-830
  *   mjw_rays_bvh / mjw_render_bvh <- the same with a static BVH per mesh (no BVH over the geoms, none to refit)
  *   mjw_inverse           <- inverse.inverse's constraint + combine  inverse.py, solver.py init_context(grad=False)
+ *   mjw_island            <- island.island (connected components by union-find, no tree x tree matrix) island.py:246-265
  *
  * Ownership: the caller owns every buffer (device pointers below); the library
  * never allocates or frees device memory and keeps no global mutable state.
@@ -439,6 +440,37 @@ int mjw_render_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_mode
  * nworld <= 0 is a successful no-op without a launch; null model / data / arrays give -1, a dense-path model with
  * nv > 64 gives -2. */
 int mjw_inverse(const mjw_model_t* m, const mjw_data_t* d, void* stream);
+
+/* Constraint islands (island.py `island`, MuJoCo's mj_island): which kinematic trees the active constraint rows of
+ * each world couple.  It stays out of mjw_model_t / mjw_data_t like mjw_ray_model_t: the tree ids and the four
+ * outputs, every pointer a device pointer. */
+typedef struct mjw_island_t {
+  int32_t ntree;   /* must equal mjw_model_t.ntree */
+  int32_t pad_;
+  const int32_t* body_treeid;  /* (nbody,) -1: static */
+  const int32_t* dof_treeid;   /* (nv,) */
+  int32_t* nisland;            /* (nworld,) */
+  int32_t* tree_island;        /* (nworld, ntree) */
+  int32_t* dof_island;         /* (nworld, nv) */
+  int32_t* efc_island;         /* (nworld, njmax) */
+} mjw_island_t;
+int mjw_sizeof_island(void);
+/* trees per world up to which the launch keeps its union-find in LDS; above it the world's tree_island / dof_island
+ * rows are the scratch (same results) */
+int mjw_island_lds_trees(void);
+/* One launch, one workgroup per world, over the rows r < n = min(nefc, njmax) the last position stage left.  The trees
+ * of a row: connect / weld rows the trees of their two bodies (through site_bodyid with site semantics), dof friction
+ * rows dof_treeid[efc_id], joint limit rows dof_treeid[jnt_dofadr[efc_id]], contact rows with two geoms the trees of
+ * the geoms' bodies (efc_id: the contact's pool slot), every other row (joint / tendon / flex equalities, tendon
+ * friction and limits, contacts with a flex side) dof_treeid of the dofs with a non-zero entry in its row of efc_J
+ * (either layout); tree ids < 0 are dropped, an id outside its array contributes nothing.  Islands are the connected
+ * components of the trees some row touches, numbered in ascending order of their smallest tree (the reference's
+ * upper-triangle edges of generic rows lose components; this does not).  Writes nisland, tree_island (-1:
+ * unconstrained), dof_island = tree_island[dof_treeid] and efc_island (the island of the row's trees, -1 for a row
+ * without trees and for every r >= n) and nothing else; allocates nothing (graph capturable).  ntree == 0 zeroes
+ * nisland without a launch; nworld <= 0 is a successful no-op; null arguments give -1, an ntree that differs from
+ * the model's -4. */
+int mjw_island(const mjw_model_t* m, const mjw_data_t* d, const mjw_island_t* is, void* stream);
 
 #ifdef __cplusplus
 }

@@ -365,6 +365,12 @@ def put_model(mjm, device=None) -> types.Model:
     chain[i] = 1 + (chain[dof_parent[i]] if dof_parent[i] >= 0 else 0)
   maxchain = int(chain.max()) if nv else 0
   m.ntree = len(starts)
+  # island discovery (island.py; the side struct mjw_island_t is built from these at call time): the tree of every
+  # dof, and of every body through the body it is welded to (-1: welded to the world)
+  dof_treeid = (np.searchsorted(tree_dofadr, np.arange(nv), side="right") - 1).astype(np.int32)
+  body_dofadr = np.asarray(mjm.body_dofadr)
+  body_treeid = np.array([dof_treeid[body_dofadr[w]] if w > 0 else -1 for w in np.asarray(mjm.body_weldid)], dtype=np.int32)
+  m.dof_treeid, m.body_treeid = _i32(dof_treeid, dev), _i32(body_treeid, dev)
   nflex = int(getattr(mjm, "nflex", 0))
   # tendon rows (friction, limit: one tendon's Jacobian row; equality: the union of two) fit a J row too
   ten_w = int(max(mjm.ten_J_rownnz)) if getattr(mjm, "ntendon", 0) else 0
@@ -768,6 +774,11 @@ def _alloc_data(m, nworld, nconmax, njmax, naconmax, device, nccdmax=None, njmax
   for name, shp in cint.items():
     _set_data_field(d, name, torch.zeros((naconmax,) + shp, dtype=torch.int32, device=device))
   d.contact.efc_address.fill_(-1)
+  # island outputs (island.py; mjw_island): they travel in the side struct mjw_island_t, not in mjw_data_t
+  d.nisland = torch.zeros(nworld, dtype=torch.int32, device=device)
+  d.tree_island = torch.full((nworld, m.ntree), -1, dtype=torch.int32, device=device)
+  d.dof_island = torch.full((nworld, m.nv), -1, dtype=torch.int32, device=device)
+  d.efc_island = torch.full((nworld, njmax), -1, dtype=torch.int32, device=device)
   # nacon and ncollision adjacent (one 8-B aligned allocation): the dense step kernel adds a world's
   # broadphase pairs and its contact slots with one 64-bit atomic (mjw_step.hip collision_and_constraints)
   counters = torch.zeros(2, dtype=torch.int32, device=device)
@@ -964,7 +975,7 @@ def reset_data(m: types.Model, d: types.Data, reset: Optional[torch.Tensor] = No
   For every world where `reset` is True (all worlds when it is None): qpos <- qpos0 (batched, indexed by
   world), eq_active <- eq_active0, mocap_pos / mocap_quat <- body_pos / body_quat of the mocap bodies;
   qvel, act, ctrl, qacc_warmstart, qfrc_applied, xfrc_applied, qacc, act_dot, sensordata, energy, time, qM,
-  solver_niter and the ne / nf / nl / nefc counters cleared; that world's contacts in the global pool
+  solver_niter and the ne / nf / nl / nefc counters cleared; nisland 0 and the island maps -1; that world's contacts in the global pool
   cleared (efc_address -1, reset_contact :1575-1622).  The pool counter nacon is cleared only when world 0
   is reset (the reference does it from world 0's thread, :1558-1559), and after the contact clear
   (the clear reads nacon, :1577)."""
@@ -997,6 +1008,10 @@ def reset_data(m: types.Model, d: types.Data, reset: Optional[torch.Tensor] = No
       t[idx] = 0
   for name in ("time", "solver_niter", "ne", "nf", "nl", "nefc"):
     getattr(d, name)[idx] = 0
+  d.nisland[idx] = 0
+  for t in (d.tree_island, d.dof_island, d.efc_island):
+    if t.numel():
+      t[idx] = -1
   if d.eq_active.numel():
     d.eq_active[idx] = m.eq_active0.to(torch.int32)
   if d.mocap_pos.numel():
