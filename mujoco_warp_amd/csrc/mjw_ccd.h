@@ -357,6 +357,17 @@ __device__ __forceinline__ GjkOut gjk(const CcdWS& w, float tolerance, int itera
     if (n + 1 == 4) { ld3(s3, w.simplex(0, 3)); S3D(c4, s0, s1, s2, s3); }
     else if (n + 1 == 3) { S2D(c4, s0, s1, s2); c4[3] = 0.0f; }
     else if (n + 1 == 2) { S1D(c4, s0, s1); c4[2] = c4[3] = 0.0f; }
+    {
+      // the barycentric coordinates are quotients of small determinants once the simplex has nearly collapsed: in
+      // fp32 they can then sum to 0.9 or 1.1, and the "closest point" leaves the simplex -- a distance below the true
+      // one (tests/ccd_cases.py, capsule-ellipsoid).  Scaled back to sum 1 they name a point of the simplex again.
+      // Smooth supports only: a discrete pair (boxes, meshes, no margin) has no such run of ever closer vertices.
+      if (!discrete && n + 1 >= 3) {
+        const float cs = c4[0] + c4[1] + c4[2] + c4[3];
+        if (cs > 0.0f && fabsf(cs - 1.0f) > 1e-4f)
+          for (int i = 0; i < 4; i++) c4[i] /= cs;
+      }
+    }
     n = 0;
     for (int i = 0; i < 4; i++) {
       if (c4[i] == 0.0f) continue;

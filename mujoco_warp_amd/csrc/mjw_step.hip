@@ -3420,6 +3420,8 @@ int launch_generic(const mjw_model_t* m, const mjw_data_t* d, hipStream_t s, con
         (void)hipFuncSetAttribute((const void*)mjw::ccd_hf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       });
       const mjw::Lay LC = mjw::make_layout(*m, d->njmax, nofactor, true);
+      // the pre-pass layout takes its own block for the convex workspace when that does not fit an aliased region
+      if ((size_t)LC.total * 4 > 160 * 1024) { g_err = std::string(name) + ": the convex pre-pass's per-world LDS (opt.ccd_iterations) exceeds 160 KiB"; return -3; }
       if (m->nhfield > 0) {
         hipLaunchKernelGGL(mjw::ccd_hf_kernel, dim3(count), dim3(64), (size_t)LC.total * 4, s, *m, *d, LC, w0);
         mjw::trace_launch(s, mjw::K_CCD_HF);

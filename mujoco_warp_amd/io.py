@@ -354,6 +354,17 @@ def put_model(mjm, device=None) -> types.Model:
   m.ccd_epa_iterations = 16 if nconvex and nboxbox == nconvex else int(getattr(mjm.opt, "ccd_iterations", 35))
   if m.nsensorccd and 37 * mjm.nbody + 14 * mjm.nv + _ccd_words(m.ccd_epa_iterations, m.nmaxpolygon, m.nmaxmeshdeg) + 368 * (m.nhfield > 0) + 32 * m.nsensorcollision > 16384:
     raise NotImplementedError("collision sensors on convex pairs: the sensor kernel's 64 KB of LDS is exceeded by this model.")
+  # the convex pre-pass kernels size their LDS workspace by the EPA iteration cap (EPA itself stops at 1000
+  # iterations, so the 10-bit vertex ids of a face word always hold): the sparse path launches them with the
+  # default 64 KB limit (workspace + 64 words), the dense path with at most 160 KiB.  The dense pre-pass's LDS is the
+  # whole per-world layout, which depends on njmax: what can never fit is refused here, and the launcher refuses the
+  # rest by name (an error return before anything is launched), as it does for every layout past 160 KiB
+  if m.nxn_ccd:
+    ccd_bytes = 4 * (_ccd_words(m.ccd_epa_iterations, m.nmaxpolygon, m.nmaxmeshdeg) + 368 * (m.nhfield > 0) + 64)
+    if ccd_bytes > (64 if m.is_sparse else 160) * 1024:
+      raise NotImplementedError(
+        f"opt.ccd_iterations = {m.ccd_epa_iterations}: the convex collision workspace ({ccd_bytes} bytes) exceeds the "
+        f"{64 if m.is_sparse else 160} KiB of LDS the {'sparse' if m.is_sparse else 'dense'} path's pre-pass kernel can have.")
 
   # sparse path: kinematic trees as dof ranges (a tree starts at every dof without a parent dof),
   # J row width = the longest union of two dof chains (+ the 6 dofs of a flex edge)

@@ -4132,6 +4132,39 @@ int orc_kat_ccd_model(const int* type, const real* pos, const real* mat, const r
   return ncon;
 }
 
+/* orc_kat_ccd_model, also filling trace[ORC_CCD_TRACE_WORDS] (ccd_trace, oracle_ccd.h) with the branches taken */
+int orc_kat_ccd_trace(const int* type, const real* pos, const real* mat, const real* size, const real* mesh_vert, const int* vertadr,
+                      const int* vertnum, real margin, real tolerance, int iterations, int multiccd, const orc_model* pm,
+                      const int* meshid, real* out, int* trace) {
+  ccd_trace t;
+  memset(&t, 0, sizeof(t));
+  t.poly_np = -1;
+  g_ccd_trace = trace ? &t : NULL;
+  int n = orc_kat_ccd_model(type, pos, mat, size, mesh_vert, vertadr, vertnum, margin, tolerance, iterations, multiccd, pm, meshid, out);
+  g_ccd_trace = NULL;
+  if (trace) memcpy(trace, &t, sizeof(t));
+  return n;
+}
+
+/* n cases in the device known-answer record layout (csrc/mjw_kat.hip: 48 reals in, 8 out: ncon dist x1 x2),
+ * no polygon data; trace (n x ORC_CCD_TRACE_WORDS) may be NULL */
+void orc_kat_ccd_batch(int n, const real* rec, const real* mesh_vert, real* out, int* trace) {
+  for (int c = 0; c < n; c++) {
+    const real* r = rec + 48 * (long)c;
+    int type[2] = {(int)r[0], (int)r[1]}, va[2] = {(int)r[36], (int)r[38]}, vn[2] = {(int)r[37], (int)r[39]};
+    real pos[6], mat[18], size[6], o[7];
+    for (int k = 0; k < 2; k++) {
+      memcpy(pos + 3 * k, r + 2 + 15 * k, 3 * sizeof(real));
+      memcpy(mat + 9 * k, r + 5 + 15 * k, 9 * sizeof(real));
+      memcpy(size + 3 * k, r + 14 + 15 * k, 3 * sizeof(real));
+    }
+    int nc = orc_kat_ccd_trace(type, pos, mat, size, mesh_vert, va, vn, r[32], r[33], (int)r[34], r[35] != 0, NULL, NULL, o,
+                               trace ? trace + ORC_CCD_TRACE_WORDS * (long)c : NULL);
+    out[8 * (long)c] = (real)nc;
+    memcpy(out + 8 * (long)c + 1, o, 7 * sizeof(real));
+  }
+}
+
 /* collision_primitive_core_test.py: sphere_triangle (gt = SPHERE), box_triangle, capsule_triangle and
  * cylinder_triangle (collision_primitive_core.py:1518-1990); capsule / cylinder take their axis from column
  * 2 of `gr`.  out = 2 x (dist, pos[3], normal[3]); returns the number of candidates. */

@@ -191,6 +191,12 @@ void orc_kat_efc_row(int disableflags, real timestep, real pos_aref, real pos_im
 int orc_kat_ccd_model(const int* type, const real* pos, const real* mat, const real* size, const real* mesh_vert, const int* vertadr,
                       const int* vertnum, real margin, real tolerance, int iterations, int multiccd, const orc_model* pm,
                       const int* meshid, real* out);
+/* the same with the branches taken (oracle_ccd.h ccd_trace, 16 ints), and over n device-layout records */
+int orc_kat_ccd_trace(const int* type, const real* pos, const real* mat, const real* size, const real* mesh_vert, const int* vertadr,
+                      const int* vertnum, real margin, real tolerance, int iterations, int multiccd, const orc_model* pm,
+                      const int* meshid, real* out, int* trace);
+void orc_kat_ccd_batch(int n, const real* rec, const real* mesh_vert, real* out, int* trace);
+long orc_ccd_renorm_count(int reset);
 int orc_kat_wrap(int fn, const real* a, int ind, real radius, real* out);
 int orc_kat_geom_triangle(int gt, const real* gp, const real* gr, const real* gs, const real* tri, real tr, real* out);
 void orc_ctrl_noise(const orc_model* m, real* ctrl, const real* center, int ncenter, int step, real std,

@@ -46,6 +46,27 @@ typedef struct {
 
 static inline real ccd_sign(real x) { return x < 0 ? -1 : 1; } /* wp.sign */
 
+/* test hook (tests/ccd_cases.py): when set, ccd_raw and multicontact record which branches one pair took, so
+   that a test can prove its input reaches the edge it is named after.  Nothing reads the record back: results
+   are the same with and without it.  Single-threaded callers only.
+   route: 0 none (GJK answered), 2 / 3 / 4 the polytope builder that made the polytope, 23 / 43 polytope2 /
+   polytope4 falling through to polytope3.  status: the builder's return (0: EPA ran).
+   epa_exit: 0 EPA did not run, 1 converged, 2 repeated vertex, 3 iterations exhausted, 4 no valid face,
+   5 face array full, 6 horizon overflow, 7 degenerate face, 8 lower2 > upper2. */
+#define ORC_CCD_TRACE_WORDS 16
+typedef struct {
+  int gjk_iter, gjk_dim, route, status, epa_iter, epa_exit, nvert, nface, horizon, multi, poly_np, cap_vert, cap_face, inflated,
+      attach_fail, ngjk;
+} ccd_trace;
+static ccd_trace* g_ccd_trace = NULL;
+/* how often gjk scaled its barycentric coordinates back to sum 1 (not in the reference; a test pins it at 0 in fp64) */
+static long g_ccd_renorm = 0;
+long orc_ccd_renorm_count(int reset) {
+  long n = g_ccd_renorm;
+  if (reset) g_ccd_renorm = 0;
+  return n;
+}
+
 /* collision_gjk.py:97-190 support (primitive types) */
 static ccd_sp ccd_support(const ccd_geom* g, const real* dir) {
   ccd_sp sp;
@@ -257,7 +278,9 @@ static gjk_result gjk(real tolerance, int iterations, const ccd_geom* g1, const 
   int n = 0;
   real xk[3] = {x1_0[0] - x2_0[0], x1_0[1] - x2_0[1], x1_0[2] - x2_0[2]};
   real xnorm_old = CCD_FLOAT_MAX;
+  if (g_ccd_trace) { g_ccd_trace->ngjk++; g_ccd_trace->gjk_iter = 0; g_ccd_trace->gjk_dim = 0; }
   for (int it = 0; it < iterations; it++) {
+    if (g_ccd_trace) g_ccd_trace->gjk_iter = it + 1;
     real xnorm = dot3(xk, xk);
     if (xnorm < tol2 || fabs(xnorm_old - xnorm) < tol2) break;
     xnorm_old = xnorm;
@@ -284,6 +307,16 @@ static gjk_result gjk(real tolerance, int iterations, const ccd_geom* g1, const 
     else if (nn == 3) { S2D(coords, r.simplex[0], r.simplex[1], r.simplex[2]); coords[3] = 0; }
     else if (nn == 2) { S1D(coords, r.simplex[0], r.simplex[1]); coords[2] = coords[3] = 0; }
     else { coords[0] = 1; coords[1] = coords[2] = coords[3] = 0; }
+    { /* not in the reference: coordinates that no longer sum to 1 (fp32, a nearly collapsed simplex) are scaled back,
+         so that xk stays a point of the simplex; csrc/mjw_ccd.h does the same.  fp64 never gets there. */
+      if (!is_discrete && nn >= 3) {
+        real cs = coords[0] + coords[1] + coords[2] + coords[3];
+        if (cs > 0 && fabs(cs - 1) > (real)1e-4) {
+          g_ccd_renorm++;
+          for (int i = 0; i < 4; i++) coords[i] /= cs;
+        }
+      }
+    }
     n = 0;
     for (int i = 0; i < 4; i++) {
       if (coords[i] == 0) continue;
@@ -306,6 +339,7 @@ static gjk_result gjk(real tolerance, int iterations, const ccd_geom* g1, const 
   else { lin_comb(r.x1, n, coords, r.simplex1); lin_comb(r.x2, n, coords, r.simplex2); }
   r.dist = sqrt(dot3(xk, xk));
   r.dim = n;
+  if (g_ccd_trace) g_ccd_trace->gjk_dim = n;
   return r;
 }
 
@@ -329,9 +363,13 @@ static void pvert(const polytope* pt, int v, real* out) {
 
 /* collision_gjk.py:194-213 */
 static real attach_face(polytope* pt, int idx, int v1, int v2, int v3) {
-  if (pt->nface == pt->cap_face) return 0;
+  if (pt->nface == pt->cap_face) {
+    if (g_ccd_trace) g_ccd_trace->attach_fail = 1;
+    return 0;
+  }
   real p1[3], p2[3], p3[3], r[3];
   pvert(pt, v1, p1); pvert(pt, v2, p2); pvert(pt, v3, p3);
+  if (g_ccd_trace) g_ccd_trace->attach_fail = 2;
   if (project_origin_plane(r, p3, p2, p1)) return 0;
   pt->face[idx] = (uint32_t)(v1 + (v2 << 10) + (v3 << 20));
   memcpy(pt->face_pr[idx], r, sizeof(r));
@@ -433,6 +471,7 @@ static int add_edge(polytope* pt, int e1, int e2) {
   }
   if (n == CCD_MAX_EPAHORIZON) return -1;
   pt->horizon[n] = edge;
+  if (g_ccd_trace && n + 1 > g_ccd_trace->horizon) g_ccd_trace->horizon = n + 1;
   return n + 1;
 }
 
@@ -582,14 +621,16 @@ static int epa(real tolerance, int iterations, polytope* pt, const ccd_geom* g1,
   real epsilon = is_discrete ? 1e-15 : tolerance;
   int nvalid = pt->nface;
   if (iterations > 1000) iterations = 1000;
+  int why = 3, nit = 0; /* trace only: the exit taken and the iterations begun */
   for (int it = 0; it < iterations; it++) {
+    nit = it + 1;
     pidx = idx;
     idx = -1;
     real lower2 = CCD_FLOAT_MAX;
     for (int i = 0; i < pt->nface; i++)
       if (!(pt->face[i] & (CCD_FACE_DELETED | CCD_FACE_INVALID)) && pt->face_norm2[i] < lower2) { idx = i; lower2 = pt->face_norm2[i]; }
-    if (lower2 > upper2 || idx < 0) { idx = pidx; break; }
-    if (lower2 <= 0) break;
+    if (lower2 > upper2 || idx < 0) { why = idx < 0 ? 4 : 8; idx = pidx; break; }
+    if (lower2 <= 0) { why = 7; break; }
     real lower = sqrt(lower2);
     int wi = pt->nvert;
     real dir[3] = {pt->face_pr[idx][0] / lower, pt->face_pr[idx][1] / lower, pt->face_pr[idx][2] / lower};
@@ -599,12 +640,12 @@ static int epa(real tolerance, int iterations, polytope* pt, const ccd_geom* g1,
     pt->nvert++;
     real upper_k = dot3(dir, w);
     if (upper_k < upper) { upper = upper_k; upper2 = upper * upper; }
-    if (upper - lower < epsilon) break;
+    if (upper - lower < epsilon) { why = 1; break; }
     if (is_discrete) {
       int rep = 0;
       for (int i = 0; i < pt->nvert - 1; i++)
         if (pt->vert_index[2 * i] == pt->vert_index[2 * wi] && pt->vert_index[2 * i + 1] == pt->vert_index[2 * wi + 1]) { rep = 1; break; }
-      if (rep) break;
+      if (rep) { why = 2; break; }
     }
     nvalid--;
     pt->face[idx] |= CCD_FACE_DELETED;
@@ -613,7 +654,7 @@ static int epa(real tolerance, int iterations, polytope* pt, const ccd_geom* g1,
     pt->nhorizon = add_edge(pt, f[0], f[1]);
     pt->nhorizon = add_edge(pt, f[1], f[2]);
     pt->nhorizon = add_edge(pt, f[2], f[0]);
-    if (pt->nhorizon == -1) { idx = -1; break; }
+    if (pt->nhorizon == -1) { why = 6; idx = -1; break; }
     for (int i = 0; i < pt->nface; i++) {
       if (pt->face[i] & CCD_FACE_DELETED) continue;
       if (dot3(pt->face_pr[i], w) - pt->face_norm2[i] > 1e-10) {
@@ -623,19 +664,26 @@ static int epa(real tolerance, int iterations, polytope* pt, const ccd_geom* g1,
         pt->nhorizon = add_edge(pt, f[0], f[1]);
         pt->nhorizon = add_edge(pt, f[1], f[2]);
         pt->nhorizon = add_edge(pt, f[2], f[0]);
-        if (pt->nhorizon == -1) { idx = -1; break; }
+        if (pt->nhorizon == -1) { why = 6; idx = -1; break; }
       }
     }
     for (int i = 0; i < pt->nhorizon; i++) {
       int e0 = pt->horizon[i] & 0x3FF, e1 = (pt->horizon[i] >> 10) & 0x3FF;
       real d2 = attach_face(pt, pt->nface, wi, e0, e1);
-      if (d2 == 0) { idx = -1; break; }
+      if (d2 == 0) { why = (g_ccd_trace && g_ccd_trace->attach_fail == 1) ? 5 : 7; idx = -1; break; }
       pt->nface++;
       if (d2 >= lower2 && d2 <= upper2) nvalid++;
       else pt->face[pt->nface - 1] |= CCD_FACE_INVALID;
     }
-    if (nvalid == 0 || idx == -1) break;
+    if (idx == -1) break;
+    if (nvalid == 0) { why = 4; break; }
     pt->nhorizon = 0;
+  }
+  if (g_ccd_trace) {
+    g_ccd_trace->epa_iter = nit;
+    g_ccd_trace->epa_exit = why;
+    g_ccd_trace->nvert = pt->nvert;
+    g_ccd_trace->nface = pt->nface;
   }
   if (idx > -1) {
     *dist = epa_witness(pt, idx, g1, g2, x1, x2);
@@ -856,6 +904,7 @@ static int polygon_clip(real face1[][3], int nface1, real face2[][3], int nface2
     np = nc;
     nc = 0;
   }
+  if (g_ccd_trace) g_ccd_trace->poly_np = np;
   if (np < 1) return 0;
   if (np > 4) {
     int q[4];
@@ -972,6 +1021,7 @@ static int multicontact(const polytope* pt, int fidx, const real* x1, const real
                         real w1[4][3], real w2[4][3]) {
   memcpy(w1[0], x1, 3 * sizeof(real));
   memcpy(w2[0], x2, 3 * sizeof(real));
+  if (g_ccd_trace) g_ccd_trace->multi = 1;
   int face[3];
   face_verts(pt->face[fidx], face);
   int fi1[3], fi2[3];
@@ -1065,6 +1115,7 @@ static int ccd_raw(const ccd_geom* g1in, const ccd_geom* g2in, real tolerance, r
     cutoff += full1 + full2;
     r = gjk(tolerance, gjk_iter, &g1, &g2, g1.pos, g2.pos, cutoff, discrete);
     if (r.dist > tolerance) { /* shallow penetration: inflate (collision_gjk.py:194-213 _inflate) */
+      if (g_ccd_trace) g_ccd_trace->inflated = 1;
       if (r.dist == CCD_FLOAT_MAX) {
         *dist = r.dist;
         memcpy(x1, r.x1, 3 * sizeof(real));
@@ -1102,15 +1153,21 @@ static int ccd_raw(const ccd_geom* g1in, const ccd_geom* g2in, real tolerance, r
   memset(pt, 0, sizeof(*pt));
   pt->cap_vert = 10 + 2 * epa_iter;
   pt->cap_face = 6 + CCD_MAX_EPAFACES * epa_iter;
-  int status;
+  int status, route = r.dim;
   if (r.dim == 2) {
     status = polytope2(pt, &r, &g1, &g2);
-    if (status == -1) status = polytope3(pt, r.dist, &r, &g1, &g2);
+    if (status == -1) { route = 23; status = polytope3(pt, r.dist, &r, &g1, &g2); }
   } else if (r.dim == 4) {
     status = polytope4(pt, &r);
-    if (status == -1) status = polytope3(pt, r.dist, &r, &g1, &g2);
+    if (status == -1) { route = 43; status = polytope3(pt, r.dist, &r, &g1, &g2); }
   } else {
     status = polytope3(pt, r.dist, &r, &g1, &g2);
+  }
+  if (g_ccd_trace) {
+    g_ccd_trace->route = route;
+    g_ccd_trace->status = status;
+    g_ccd_trace->cap_vert = pt->cap_vert / 2;
+    g_ccd_trace->cap_face = pt->cap_face;
   }
   if (status) return 1; /* origin on the boundary: not penetrating */
   int f = epa(tolerance, epa_iter, pt, &g1, &g2, discrete, dist, x1, x2);

@@ -317,10 +317,42 @@ def kat_upper_trid_index(n, i, j):
   return _lib(64).orc_upper_trid_index(n, i, j)
 
 
+# oracle_ccd.h ccd_trace
+CCD_TRACE_WORDS = 16
+CCD_TRACE_FIELDS = ("gjk_iter", "gjk_dim", "route", "status", "epa_iter", "epa_exit", "nvert", "nface", "horizon", "multi",
+                    "poly_np", "cap_vert", "cap_face", "inflated", "attach_fail", "ngjk")
+CCD_EPA_EXITS = {0: "none", 1: "converged", 2: "repeated vertex", 3: "iterations exhausted", 4: "no valid face",
+                 5: "face array full", 6: "horizon overflow", 7: "degenerate face", 8: "lower2 > upper2"}
+
+
+def ccd_renorm_count(real_bits=64, reset=False):
+  """How often this build's gjk scaled its barycentric coordinates back to sum 1 since the last reset."""
+  f = _lib(real_bits).orc_ccd_renorm_count
+  f.restype = ctypes.c_long
+  return int(f(ctypes.c_int(int(reset))))
+
+
+def kat_ccd_batch(recs, mesh_vert=None, real_bits=64, trace=False):
+  """kat_ccd over (n, 48) records in the device's known-answer layout (csrc/mjw_kat.hip; vertadr absolute into
+  mesh_vert): (n, 8) = ncon dist x1 x2, and with trace=True the (n, CCD_TRACE_WORDS) int trace."""
+  lib = _lib(real_bits)
+  creal = ctypes.c_double if real_bits == 64 else ctypes.c_float
+  dt = np.float64 if real_bits == 64 else np.float32
+  # the records are what the device reads: fp32 values, whatever the oracle then computes in
+  r = np.ascontiguousarray(np.asarray(recs, np.float32).astype(dt).reshape(-1, 48))
+  mv = np.ascontiguousarray(np.asarray(np.zeros(3) if mesh_vert is None else mesh_vert, np.float32).astype(dt).reshape(-1))
+  out = np.zeros((len(r), 8), dt)
+  tr = np.zeros((len(r), CCD_TRACE_WORDS), np.int32)
+  lib.orc_kat_ccd_batch(ctypes.c_int(len(r)), r.ctypes.data_as(ctypes.POINTER(creal)), mv.ctypes.data_as(ctypes.POINTER(creal)),
+                        out.ctypes.data_as(ctypes.POINTER(creal)), tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if trace else None)
+  return (out.astype(np.float64), tr) if trace else out.astype(np.float64)
+
+
 def kat_ccd(types, pos, mat, size, margin, tolerance, iterations, multiccd, mesh_vert=None, vertadr=(0, 0), vertnum=(0, 0),
-            real_bits=64, mjm=None, meshid=None):
+            real_bits=64, mjm=None, meshid=None, trace=False):
   """collision_gjk_test.py _geom_dist on the oracle: (ncon, dist, x1, x2); ncon -1 = not restated.  With the
-  compiled model `mjm` and the geoms' mesh ids, mesh geoms carry their polygon data (mesh multi-contact)."""
+  compiled model `mjm` and the geoms' mesh ids, mesh geoms carry their polygon data (mesh multi-contact).
+  trace=True appends a dict of the branches taken (CCD_TRACE_FIELDS); the result is the same either way."""
   lib = _lib(real_bits)
   creal = ctypes.c_double if real_bits == 64 else ctypes.c_float
   dt = np.float64 if real_bits == 64 else np.float32
@@ -331,6 +363,15 @@ def kat_ccd(types, pos, mat, size, margin, tolerance, iterations, multiccd, mesh
   mv = np.ascontiguousarray(np.zeros(3) if mesh_vert is None else mesh_vert, dtype=dt).reshape(-1)
   va, vn = np.ascontiguousarray(vertadr, dtype=np.int32), np.ascontiguousarray(vertnum, dtype=np.int32)
   out = np.zeros(7, dt)
+  if trace:
+    om = OracleModel(mjm, real_bits=real_bits) if mjm is not None else None
+    mid = np.ascontiguousarray(meshid if mjm is not None else (-1, -1), dtype=np.int32)
+    tr = np.zeros(CCD_TRACE_WORDS, np.int32)
+    f = lib.orc_kat_ccd_trace
+    f.restype = ctypes.c_int
+    n = f(I(t), P(pos), P(mat), P(size), P(mv), I(va), I(vn), creal(margin), creal(tolerance), ctypes.c_int(iterations),
+          ctypes.c_int(int(multiccd)), ctypes.byref(om.struct) if om else None, I(mid) if om else None, P(out), I(tr))
+    return n, float(out[0]), out[1:4].copy(), out[4:7].copy(), dict(zip(CCD_TRACE_FIELDS, (int(v) for v in tr)))
   if mjm is not None:
     om = OracleModel(mjm, real_bits=real_bits)
     mid = np.ascontiguousarray(meshid, dtype=np.int32)
