@@ -19,8 +19,9 @@
  *   mjw_sensor            <- sensor.sensor_pos/_vel/_acc  sensor.py:761,1377,2447
  *   mjw_ctrl_noise        <- benchmark.ctrl_noise         _src/benchmark.py:41-83
  *   mjw_rays              <- ray.rays (no render context) ray.py:1212-1312
- *   mjw_render            <- render.render (brute force over the geoms; no textures, no flex) render.py:515-830
+ *   mjw_render            <- render.render (brute force over the geoms; no textures) render.py:515-830
  *   mjw_rays_bvh / mjw_render_bvh <- the same with a static BVH per mesh (no BVH over the geoms, none to refit)
+ *   mjw_flex_refit / mjw_render_flex <- render.refit_bvh / render.render of a context made with render_flex
  *   mjw_inverse           <- inverse.inverse's constraint + combine  inverse.py, solver.py init_context(grad=False)
  *   mjw_island            <- island.island (connected components by union-find, no tree x tree matrix) island.py:246-265
  *
@@ -471,6 +472,65 @@ int mjw_island_lds_trees(void);
  * nisland without a launch; nworld <= 0 is a successful no-op; null arguments give -1, an ntree that differs from
  * the model's -4. */
 int mjw_island(const mjw_model_t* m, const mjw_data_t* d, const mjw_island_t* is, void* stream);
+
+/* Flex rendering (mjw_flex_refit, mjw_render_flex): the host-built tables of a render context made with
+ * render_flex, and its two per-world buffers.  It stays out of mjw_model_t / mjw_render_t like mjw_island_t; every
+ * pointer is a device pointer and every vertex / element / edge id in the tables is global (flex_vertadr /
+ * flex_elemadr / flex_edgeadr already added), so the kernels need none of the model's flex tables besides these.
+ * info: 12 ints per flex: flex_dim, flex_vertadr, flex_vertnum, first face, faces, first node, nodes, tree depth,
+ * first entry of level, flex_edgeadr, flex_edgenum, 0.  Faces (dim 2: two per element, then two per boundary
+ * fragment; dim 3: the flex_shell triangles; dim 1: none, its edges are capsules) are corner records: three per
+ * face, each (vertex, sign, source): the point is xpos[vertex] + sign * flex_radius * n with n the vertex normal
+ * (source < 0) or the flat normal of element `source`; sign 0 is the vertex itself.  node / tri: one tree per
+ * flex over its faces in the layout of mjw_bvh_t (face ids local to the flex); the boxes in `node` are the rest
+ * pose's and only its two ints are read.  level: per tree depth + 1 local node indices, the first node of each
+ * level and the node count.  node_box row w: the boxes of all nodes as mjw_flex_refit left them, then one box per
+ * flex around its vertices grown by the radius. */
+typedef struct mjw_flexrender_t {
+  int32_t nflex;       /* must equal mjw_model_t.nflex */
+  int32_t nflexvert;   /* must equal mjw_model_t.nflexvert */
+  int32_t nflexelem;   /* must equal mjw_model_t.nflexelem */
+  int32_t nflexedge;   /* must equal mjw_model_t.nflexedge */
+  int32_t nface;       /* faces of all flexes: rows of corner / 3, entries of tri */
+  int32_t nnode;       /* nodes of all trees */
+  int32_t ninc;        /* entries of inc */
+  int32_t nlevel;      /* entries of level */
+  int32_t leaf_size;   /* faces per leaf at the most; at most 4 */
+  int32_t max_depth;   /* levels of the deepest tree; at most 32 */
+  int32_t min_faces;   /* flexes with fewer faces are intersected by the loop over their faces (same results) */
+  int32_t pad_;
+  const int32_t* info;        /* (nflex, 12) */
+  const float* flex_radius;   /* (nflex,) */
+  const float* flex_rgba;     /* (nflex, 4) */
+  const int32_t* corner;      /* (nface, 3, 3) */
+  const int32_t* elem_vert;   /* (nflexelem, 3) the vertices of the dim-2 elements (flex_elem) */
+  const int32_t* edge_vert;   /* (nflexedge, 2) flex_edge */
+  const int32_t* inc_adr;     /* (nflexvert + 1,) vertex -> incident dim-2 elements, ascending: a CSR */
+  const int32_t* inc;         /* (ninc,) */
+  const float* node;          /* (nnode, 8) */
+  const int32_t* tri;         /* (nface,) */
+  const int32_t* level;       /* (nlevel,) */
+  float* node_box;            /* (nworld, nnode + nflex, 6) minimum, maximum */
+  float* vert_norm;           /* (nworld, nflexvert, 3) vertex normals of the dim-2 flexes */
+} mjw_flexrender_t;
+int mjw_sizeof_flexrender(void);
+/* Refits every flex tree of every world to d->flexvert_xpos: one launch, one workgroup per (world, flex): the vertex
+ * normals of a dim-2 flex (the normalised sum of its incident elements' unit normals in ascending element order; a
+ * zero sum stays zero), every leaf's box as the exact float32 minimum / maximum of its faces' points, the inner
+ * nodes level by level from the deepest up, and the whole-flex box.  Writes fr->node_box and fr->vert_norm and
+ * nothing else; no atomics, graph capturable.  nflex == 0 or nworld <= 0 is a successful no-op; null arguments or
+ * tables give -1; counts that differ from the model's, a leaf_size above 4 or a max_depth above 32 give -4; more
+ * workgroups than the grid holds -2. */
+int mjw_flex_refit(const mjw_model_t* m, const mjw_data_t* d, const mjw_flexrender_t* fr, void* stream);
+/* mjw_render_bvh (bvh != NULL) or mjw_render (bvh == NULL: the meshes' faces are looped over) with the flexes of
+ * `fr` drawn as well, from the boxes and normals the last mjw_flex_refit left: it does not refit.  The nearest hit
+ * over geoms and flexes; a flex replaces a geom only when strictly nearer, the lower flex id and within a flex the
+ * lower face id win ties.  A flex pixel has segmentation -2, the colour flex_rgba and, on a triangle, the winding
+ * normal turned to face the ray; flexes throw and receive shadows like geoms.  Flexes of at least min_faces faces
+ * are walked through their tree, smaller ones face by face, with the same images bit for bit.  With nflex == 0 it
+ * is mjw_render_bvh / mjw_render.  Errors as those calls and mjw_flex_refit. */
+int mjw_render_flex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
+                    const mjw_flexrender_t* fr, void* stream);
 
 #ifdef __cplusplus
 }

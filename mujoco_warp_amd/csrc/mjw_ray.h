@@ -473,51 +473,88 @@ __device__ __forceinline__ void stage_chunk(const GeomArgs& a, int wid, int g0, 
 // the grown slab, and no 0 * inf is formed.  The entry distance is compared after a cut of 2^-10: ray_triangle's
 // distance carries a relative error of about 1e-7 / sin(grazing angle), so the comparison stays on the safe side
 // down to grazing angles of 1e-4 rad.  ANYHIT: a lane leaves the walk at its first hit under `best`.
-template <bool ANYHIT>
-__device__ __forceinline__ float mesh_bvh(const BvhArgs& bv, int mesh, const float* vert, const int* face, int nface, bool cand,
-                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl) {
-  float x = -1.0f;
-  if (mesh >= bv.nmesh) return x;  // (uniform, like every test of the tables below: a table that does not fit hits nothing)
-  const int* adr = bv.adr + 4 * (long)mesh;
-  const int nadr = uni(adr[0]), nnode = uni(adr[1]), triadr = uni(adr[2]);
-  if (nadr < 0 || nnode < 1 || nadr > bv.nnode - nnode || triadr < 0 || triadr > bv.ntri - nface) return x;  // (uniform)
-  const float* nodes = bv.node + 8 * (long)nadr;
-  const int* tri = bv.tri + triadr;
+//
+// The walk is one routine for every kind of tree (bvh_walk).  `nodes` is the static node table of the tree, read for
+// its two ints; a source says where a node's box lies and how a leaf item becomes three points:
+//   src.box(node)            six floats, the minimum and the maximum (node 0: the root, which also sets the padding)
+//   src.points(f, p0, p1, p2) the triangle of item f; false: there is none (an id outside its table)
+// A mesh's boxes are the static table's own and its points the vertices mesh_face names (MeshSrc); a flex's boxes are
+// this world's refit rows and its points are made on the fly (mjw_flexrender.h FlexSrc).
 
-  const float vmax = fmaxf(fabsf(lv[0]), fmaxf(fabsf(lv[1]), fabsf(lv[2])));
+// the reciprocal direction of a ray for the slab test; a component under 1e-12 of the largest counts as zero
+struct RaySlab {
   float inv[3];
   bool par[3];
+};
+__device__ __forceinline__ void ray_slab(const float* lv, RaySlab& s) {
+  const float vmax = fmaxf(fabsf(lv[0]), fmaxf(fabsf(lv[1]), fabsf(lv[2])));
   for (int i = 0; i < 3; i++) {
-    par[i] = !(fabsf(lv[i]) > 1e-12f * vmax);
-    inv[i] = par[i] ? 0.0f : 1.0f / lv[i];
+    s.par[i] = !(fabsf(lv[i]) > 1e-12f * vmax);
+    s.inv[i] = s.par[i] ? 0.0f : 1.0f / lv[i];
   }
+}
+// the padding of the slab test for a ray from lp into a tree (or a box) whose outermost box is `root`
+__device__ __forceinline__ float slab_pad(const float* root, const float* lp) {
   float pad = fabsf(lp[0]) + fabsf(lp[1]) + fabsf(lp[2]);
-  for (int i = 0; i < 3; i++) pad += fmaxf(fabsf(nodes[i]), fabsf(nodes[3 + i]));
-  pad = pad * 1e-5f + 1e-30f;
+  for (int i = 0; i < 3; i++) pad += fmaxf(fabsf(root[i]), fabsf(root[3 + i]));
+  return pad * 1e-5f + 1e-30f;
+}
+// does the ray meet the box nd (minimum, maximum) grown by pad, and where does it enter (tmin >= 0)
+__device__ __forceinline__ bool slab_test(const float* nd, float pad, const float* lp, const RaySlab& s, float& tmin) {
+  float tmax = MJW_MAXVAL;
+  tmin = 0.0f;
+  for (int i = 0; i < 3; i++) {
+    const float a = nd[i] - pad - lp[i], b = nd[3 + i] + pad - lp[i];  // a <= 0 <= b: the origin is in the slab
+    float t0, t1;
+    if (s.par[i]) {
+      const bool in = a <= 0.0f && b >= 0.0f;
+      t0 = in ? -MJW_MAXVAL : MJW_MAXVAL;
+      t1 = in ? MJW_MAXVAL : -MJW_MAXVAL;
+    } else {
+      t0 = fminf(a * s.inv[i], b * s.inv[i]);
+      t1 = fmaxf(a * s.inv[i], b * s.inv[i]);
+    }
+    tmin = fmaxf(tmin, t0);
+    tmax = fminf(tmax, t1);
+  }
+  return tmin <= tmax;
+}
+
+struct MeshSrc {
+  const float* nodes;  // the mesh's first node
+  const float* vert;   // the mesh's first vertex
+  const int* face;     // the mesh's first face
+  __device__ __forceinline__ const float* box(int node) const { return nodes + 8 * node; }
+  __device__ __forceinline__ bool points(int f, float* p0, float* p1, float* p2) const {
+    const int* idx = face + 3 * (long)f;
+    const float *v0 = vert + 3 * idx[0], *v1 = vert + 3 * idx[1], *v2 = vert + 3 * idx[2];
+    for (int i = 0; i < 3; i++) {
+      p0[i] = v0[i];
+      p1[i] = v1[i];
+      p2[i] = v2[i];
+    }
+    return true;
+  }
+};
+
+template <bool ANYHIT, class Src>
+__device__ __forceinline__ float bvh_walk(const Src& src, const float* nodes, int nnode, const int* tri, int nface, bool cand,
+                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl) {
+  float x = -1.0f;
+  RaySlab slab;
+  ray_slab(lv, slab);
+  const float pad = slab_pad(src.box(0), lp);
 
   int bf = 0x7fffffff;  // the face of x
   const int lane = (int)(threadIdx.x & 63u);
   int stack = 0, sp = 0, node = 0;
   for (;;) {
-    const float* nd = nodes + 8 * node;
-    const int ia = uni(reinterpret_cast<const int*>(nd)[6]), ib = uni(reinterpret_cast<const int*>(nd)[7]);
-    float tmin = 0.0f, tmax = MJW_MAXVAL;
-    for (int i = 0; i < 3; i++) {
-      const float a = nd[i] - pad - lp[i], b = nd[3 + i] + pad - lp[i];  // a <= 0 <= b: the origin is in the slab
-      float t0, t1;
-      if (par[i]) {
-        const bool in = a <= 0.0f && b >= 0.0f;
-        t0 = in ? -MJW_MAXVAL : MJW_MAXVAL;
-        t1 = in ? MJW_MAXVAL : -MJW_MAXVAL;
-      } else {
-        t0 = fminf(a * inv[i], b * inv[i]);
-        t1 = fmaxf(a * inv[i], b * inv[i]);
-      }
-      tmin = fmaxf(tmin, t0);
-      tmax = fminf(tmax, t1);
-    }
+    const int* nd = reinterpret_cast<const int*>(nodes + 8 * node);
+    const int ia = uni(nd[6]), ib = uni(nd[7]);
+    float tmin;
+    const bool in = slab_test(src.box(node), pad, lp, slab, tmin);
     const float lim = x >= 0.0f ? fminf(x, best) : best;
-    const bool go = cand && tmin <= tmax && tmin * 0.9990234375f <= lim;
+    const bool go = cand && in && tmin * 0.9990234375f <= lim;
     const unsigned long long mask = __ballot(go);
     if (mask) {
       if (ib <= 0) {  // a leaf: its triangles, by their original face ids
@@ -526,9 +563,9 @@ __device__ __forceinline__ float mesh_bvh(const BvhArgs& bv, int mesh, const flo
           for (int i = 0; i < cnt; i++) {
             const int f = uni(tri[ia + i]);
             if ((unsigned)f >= (unsigned)nface) continue;
-            const int* idx = face + 3 * (long)f;
-            float n[3];
-            const float sol = ray_triangle(vert + 3 * idx[0], vert + 3 * idx[1], vert + 3 * idx[2], lp, lv, b0, b1, n);
+            float n[3], p0[3], p1[3], p2[3];
+            if (!src.points(f, p0, p1, p2)) continue;
+            const float sol = ray_triangle(p0, p1, p2, lp, lv, b0, b1, n);
             if (sol >= 0.0f && (x < 0.0f || sol < x || (sol == x && f < bf))) {
               x = sol;
               bf = f;
@@ -564,6 +601,17 @@ __device__ __forceinline__ float mesh_bvh(const BvhArgs& bv, int mesh, const flo
     node = uni(__builtin_amdgcn_readlane(stack, sp));
   }
   return x;
+}
+
+template <bool ANYHIT>
+__device__ __forceinline__ float mesh_bvh(const BvhArgs& bv, int mesh, const float* vert, const int* face, int nface, bool cand,
+                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl) {
+  if (mesh >= bv.nmesh) return -1.0f;  // (uniform, like every test of the tables below: a table that does not fit hits nothing)
+  const int* adr = bv.adr + 4 * (long)mesh;
+  const int nadr = uni(adr[0]), nnode = uni(adr[1]), triadr = uni(adr[2]);
+  if (nadr < 0 || nnode < 1 || nadr > bv.nnode - nnode || triadr < 0 || triadr > bv.ntri - nface) return -1.0f;  // (uniform)
+  const float* nodes = bv.node + 8 * (long)nadr;
+  return bvh_walk<ANYHIT>(MeshSrc{nodes, vert, face}, nodes, nnode, bv.tri + triadr, nface, cand, lp, lv, b0, b1, best, nl);
 }
 
 // Every lane's ray (pnt, vec; world frame) against the n staged geoms g0 ..: a hit nearer than `best` (strict

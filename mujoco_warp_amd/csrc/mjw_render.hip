@@ -12,8 +12,12 @@
 // Shading (render.py:680-769, 410-512): hemispheric ambient plus the active lights; with shadows, one any-hit
 // pass of the geom loop per shadow-casting light from the hit point towards the light, traced only by the
 // waves in which some lane faces the light.  Lights are read through wave-uniform addresses.
+//
+// Flexes (mjw_render_flex; FLEX = true): after the geom loop every ray goes through flex_loop (mjw_flexrender.h), for
+// the first hit and for each shadow ray; a flex pixel has segmentation -2, the colour flex_rgba and no material.
 #include "mjw_common.h"
 #include "mjw_ray.h"
+#include "mjw_flexrender.h"
 
 namespace mjw {
 namespace ray {
@@ -64,8 +68,8 @@ __device__ __forceinline__ void pixel_ray(float fovy, const float* sensorsize, c
   normalize3(local);
 }
 
-template <int NT, bool BVH>
-__device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& bv, float* recs) {
+template <int NT, bool BVH, bool FLEX>
+__device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& bv, const FlexArgs& fx, float* recs) {
   const int tid = threadIdx.x;
   const int wid = blockIdx.x / a.ntile, t = blockIdx.x - wid * a.ntile;
   const int ci = a.tile[4 * t], x0 = a.tile[4 * t + 1], y0 = a.tile[4 * t + 2];
@@ -99,23 +103,28 @@ __device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& 
   float best = MJW_MAXVAL, bn[3] = {0.0f, 0.0f, 0.0f};
   int bid = -1;
   geom_loop<NT, false, BVH>(a.g, bv, wid, recs, false, active, -1, pnt, vec, best, bid, bn);
-  const bool hit = bid >= 0;
+  int fid = -1;  // the flex of the hit when a flex is nearer than every geom
+  if (FLEX) flex_loop<false>(fx, wid, active, pnt, vec, best, fid, bn);
+  const bool hit = bid >= 0 || fid >= 0;
 
   const long pix = (long)py * W + px;
   const int sadr = a.seg_adr[ci], dadr = a.depth_adr[ci], cadr = a.rgb_adr[ci];
-  if (active && sadr >= 0 && sadr + pix < a.seg_ld) a.seg[(long)wid * a.seg_ld + sadr + pix] = bid;
+  if (active && sadr >= 0 && sadr + pix < a.seg_ld) a.seg[(long)wid * a.seg_ld + sadr + pix] = fid >= 0 ? -2 : bid;
   if (active && dadr >= 0 && dadr + pix < a.depth_ld) a.depth[(long)wid * a.depth_ld + dadr + pix] = hit ? best * -local[2] : 0.0f;
   if (cadr < 0) return;  // (uniform over the workgroup)
 
   // shading: every thread goes through the light loop (the shadow pass holds barriers), a lane without a hit
   // takes no part in it
-  const int gid = hit ? bid : 0;
+  const int gid = bid >= 0 ? bid : 0;
   const int matid = a.g.ngeom > 0 ? a.g.geom_matid[gid] : -1;
   const float* col = (matid >= 0 && matid < a.g.nmat) ? row(a.g.mat_rgba, a.g.matrgba_nb, (long)a.g.nmat * 4, wid) + 4 * matid
                                                        : row(a.g.geom_rgba, a.g.rgba_nb, (long)a.g.ngeom * 4, wid) + 4 * gid;
   float base[3] = {0.0f, 0.0f, 0.0f};
-  if (hit)
+  if (FLEX && fid >= 0) {
+    for (int i = 0; i < 3; i++) base[i] = fx.rgba[4 * fid + i];
+  } else if (bid >= 0) {
     for (int i = 0; i < 3; i++) base[i] = col[i];
+  }
   const float hp[3] = {pnt[0] + vec[0] * best, pnt[1] + vec[1] * best, pnt[2] + vec[2] * best};
   float n[3] = {bn[0], bn[1], bn[2]};
   if (!(dot3(n, n) > 0.0f)) { n[0] = 0.0f; n[1] = 0.0f; n[2] = 1.0f; }
@@ -153,6 +162,11 @@ __device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& 
       float sbest = type == 1 ? 1e8f : r - 1e-3f, sn[3];
       int sid = -1;
       geom_loop<NT, true, BVH>(a.g, bv, wid, recs, a.g.ngeom <= RAY_CHUNK, active && ndotl > 0.0f, -1, so, L, sbest, sid, sn);
+      if (FLEX) {
+        int sfid = -1;
+        flex_loop<true>(fx, wid, active && ndotl > 0.0f && sid < 0, so, L, sbest, sfid, sn);
+        if (sfid >= 0) sid = 0;
+      }
       if (sid >= 0) visible = 0.3f;
     }
     const float c = ndotl * att * visible;
@@ -173,27 +187,38 @@ __device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& 
 template <int NT>
 __global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
   __shared__ float recs[RAY_CHUNK * RECW];
-  render_body<NT, false>(a, BvhArgs{}, recs);
+  render_body<NT, false, false>(a, BvhArgs{}, FlexArgs{}, recs);
 }
 
 // the same with the meshes walked through the BVHs of the render context
 template <int NT>
 __global__ void __launch_bounds__(NT) render_bvh_kernel(const RenderArgs a, const BvhArgs bv) {
   __shared__ float recs[RAY_CHUNK * RECW];
-  render_body<NT, true>(a, bv, recs);
+  render_body<NT, true, false>(a, bv, FlexArgs{}, recs);
+}
+
+// the same with the flexes of the render context drawn too, the meshes through their BVHs or face by face
+template <int NT, bool BVH>
+__global__ void __launch_bounds__(NT) render_flex_kernel(const RenderArgs a, const BvhArgs bv, const FlexArgs fx) {
+  __shared__ float recs[RAY_CHUNK * RECW];
+  render_body<NT, BVH, true>(a, bv, fx, recs);
 }
 
 }  // namespace ray
 }  // namespace mjw
 
 static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
-                         bool with_bvh, void* stream) {
+                         bool with_bvh, const mjw_flexrender_t* fr, bool with_flex, void* stream) {
   using namespace mjw::ray;
   if (!m || !d || !rm || !rc) return mjw::set_last_error(-1, "mjw_render: null model / data / ray model / render context");
   BvhArgs bv;
   memset(&bv, 0, sizeof(bv));
   int walk = 0;
-  if (with_bvh && (walk = check_bvh_args("mjw_render_bvh", m, rm, bvh, bv)) < 0) return walk;
+  if (with_bvh && (walk = check_bvh_args(with_flex ? "mjw_render_flex" : "mjw_render_bvh", m, rm, bvh, bv)) < 0) return walk;
+  FlexArgs fx;
+  memset(&fx, 0, sizeof(fx));
+  int flex = 0;
+  if (with_flex && (flex = check_flex_args("mjw_render_flex", m, d, fr, fx)) < 0) return flex;
   if (rc->ntile < 0 || rc->nrender < 0) return mjw::set_last_error(-4, "mjw_render: ntile / nrender < 0");
   if (rc->ntile == 0 || d->nworld <= 0) return 0;
   if (rc->tile_threads != 64 && rc->tile_threads != 256) return mjw::set_last_error(-4, "mjw_render: tile_threads must be 64 or 256");
@@ -228,7 +253,13 @@ static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ra
   hipStream_t s = (hipStream_t)stream;
   const long nblock = (long)a.nworld * a.ntile;
   if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, "mjw_render: nworld x tiles exceeds the grid limit");
-  if (walk) {
+  if (flex) {
+    const bool small = rc->tile_threads == 64;
+    if (walk && small) hipLaunchKernelGGL((render_flex_kernel<64, true>), dim3((unsigned)nblock), dim3(64), 0, s, a, bv, fx);
+    else if (walk) hipLaunchKernelGGL((render_flex_kernel<256, true>), dim3((unsigned)nblock), dim3(256), 0, s, a, bv, fx);
+    else if (small) hipLaunchKernelGGL((render_flex_kernel<64, false>), dim3((unsigned)nblock), dim3(64), 0, s, a, bv, fx);
+    else hipLaunchKernelGGL((render_flex_kernel<256, false>), dim3((unsigned)nblock), dim3(256), 0, s, a, bv, fx);
+  } else if (walk) {
     if (rc->tile_threads == 64)
       hipLaunchKernelGGL(render_bvh_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a, bv);
     else
@@ -244,10 +275,15 @@ static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ra
 }
 
 extern "C" int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, void* stream) {
-  return render_launch(m, d, rm, rc, nullptr, false, stream);
+  return render_launch(m, d, rm, rc, nullptr, false, nullptr, false, stream);
 }
 
 extern "C" int mjw_render_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc,
                               const mjw_bvh_t* bvh, void* stream) {
-  return render_launch(m, d, rm, rc, bvh, true, stream);
+  return render_launch(m, d, rm, rc, bvh, true, nullptr, false, stream);
+}
+
+extern "C" int mjw_render_flex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc,
+                               const mjw_bvh_t* bvh, const mjw_flexrender_t* fr, void* stream) {
+  return render_launch(m, d, rm, rc, bvh, bvh != nullptr, fr, true, stream);
 }

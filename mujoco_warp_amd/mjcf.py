@@ -568,6 +568,7 @@ class _Compiler:
     return dict(
       name=name, dim=dim, bodies=bodies, elems=np.array(elems, dtype=np.int32).reshape(-1, dim + 1),
       radius=float(a.get("radius", 0.005)),
+      rgba=_merge_vec([0.5, 0.5, 0.5, 1.0], _floats(a.get("rgba", "0.5 0.5 0.5 1"))),
       edge_equality=ea.get("equality", "false") == "true",
       edge_solref=_merge_vec([0.02, 1.0], _floats(ea.get("solref", "0.02 1"))),
       edge_solimp=_merge_vec([0.9, 0.95, 0.001, 0.5, 2.0], _floats(ea.get("solimp", "0.9 0.95 0.001 0.5 2"))),
@@ -1257,6 +1258,7 @@ class _Compiler:
     m.flex_stiffness = np.array(stiffness).reshape(-1, 21)
     m.flex_damping = np.array([fc["damping"] for fc in fl])
     m.flex_radius = np.array([fc["radius"] for fc in fl])
+    m.flex_rgba = np.array([fc["rgba"] for fc in fl], dtype=np.float32).reshape(-1, 4)
     m.flex_margin = np.array([fc["margin"] for fc in fl])
     m.flex_gap = np.array([fc["gap"] for fc in fl])
     m.flex_condim = np.array([fc["condim"] for fc in fl], dtype=np.int32)

@@ -1,7 +1,7 @@
 """Batched camera rendering: segmentation, depth and shaded RGB images of a model's cameras
 (mujoco_warp/_src/render.py `render`, io.py `create_render_context`, render_util.py readers).
 
-One HIP launch (`mjw_render_bvh`, csrc/mjw_render.hip) on the Data's stream per `render` call: a workgroup per
+One HIP launch (`mjw_render_bvh`, or `mjw_render_flex` for a context made with `render_flex`; csrc/mjw_render.hip) on the Data's stream per `render` call: a workgroup per
 world, camera and 16 x 16 pixel tile makes the pixel rays from `d.cam_xpos` / `d.cam_xmat` and the per-world
 camera parameters, finds the nearest geom with the geom loop `rays` uses, and writes every pixel of every
 enabled output.  No kinematics run here: the frames are those the last position stage left.
@@ -9,10 +9,20 @@ enabled output.  No kinematics run here: the frames are those the last position 
 Meshes are intersected through a static BVH per mesh (bvh.py), built on the host when the context is made and
 walked by the kernel in place of the loop over every face, with the same result bit for bit (meshes of fewer than
 `rc.bvh_min_faces` faces, default bvh.BVH_MIN_FACES, keep the loop: the walk does not pay there).  The trees live
-in the mesh's own frame and meshes are rigid, so nothing is refit per step (`refit_bvh` does nothing).  They were
+in the mesh's own frame and meshes are rigid, so they are never refit (`refit_bvh` leaves them alone).  They were
 built from the host model's vertices: when `m.mesh_vert` is batched per world (leading dim > 1) the call falls
-back to the face loop.  There is no BVH over the geoms (they are culled by bounding ball and box per wave) or over
-heightfields, no textures, no flex rendering and no orthographic cameras.
+back to the face loop.
+
+Flexes are drawn by a context made with `render_flex=True` (the default still refuses a model with flexes): cloth as
+a shell of thickness 2 flex_radius around its elements, closed along the boundary edges, soft bodies as their
+flex_shell triangles, ropes as one capsule per edge; segmentation -2, colour `flex_rgba`.  Each flex with faces has
+a tree whose topology is built once over the rest pose and whose boxes `refit_bvh` refits to `d.flexvert_xpos`, per
+world, in one launch (`mjw_flex_refit`, csrc/mjw_flexrender.hip).  `render` does not refit: call `refit_bvh` after the
+step and before `render`, as code written for the reference does.  The faces are never stored: the context keeps
+corner records and, per world, the node boxes and the vertex normals.
+
+There is no BVH over the geoms (they are culled by bounding ball and box per wave) or over heightfields, no textures
+and no orthographic cameras.
 """
 
 from __future__ import annotations
@@ -24,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .bvh import BVH_LEAF, BVH_MAX_DEPTH, BVH_MIN_FACES, NODE_WORDS, build_mesh_bvh
+from .bvh import BVH_LEAF, BVH_MAX_DEPTH, BVH_MIN_FACES, FLEX_BVH_MIN_FACES, FLEX_INFO_WORDS, NODE_WORDS, build_flex_tables, build_mesh_bvh
 from .types import Data, Model, RenderContext
 
 TILE = 16  # pixels per side of a workgroup's tile (csrc/mjw_render.hip)
@@ -42,7 +52,7 @@ def _flags(given, ncam, mjm, active, bit, default):
 
 def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, render_depth=None, render_seg=None, use_textures: bool = True,
                           use_shadows: bool = False, enabled_geom_groups: Sequence[int] = [0, 1, 2], cam_active: Optional[Sequence[bool]] = None,
-                          flex_render_smooth: bool = True, use_precomputed_rays: bool = True, device=None) -> RenderContext:
+                          flex_render_smooth: bool = True, use_precomputed_rays: bool = True, device=None, render_flex: bool = False) -> RenderContext:
   """Creates a render context on the device (io.py:2649-2904).
 
   cam_res: one (width, height) tuple for every active camera, a list with one per active camera, or None for
@@ -52,14 +62,24 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
   use_shadows: lights with castshadow throw shadows.  The BVHs of the model's meshes are built here, on the host
   (rc.mesh_bvh_node / mesh_bvh_tri / mesh_bvh_adr; empty for a model without meshes).
 
-  Accepted and ignored: `use_textures` (the MJCF compiler keeps no textures, colours are mat_rgba / geom_rgba),
-  `flex_render_smooth` (no flex rendering) and `use_precomputed_rays` (the rays are always made in the kernel, so
-  per-world cam_fovy / cam_intrinsic work).  A model with flexes raises NotImplementedError: its flex elements
-  would be silently invisible."""
+  render_flex: draw the model's flexes (module docstring).  The context then holds the flex tables (bvh.py
+  `build_flex_tables`: rc.flex_info, flex_corner, flex_elem_vert, flex_edge_vert, flex_inc_adr, flex_inc, flex_bvh_node,
+  flex_bvh_tri, flex_bvh_level, flex_radius, flex_rgba) and two per-world buffers, rc.flex_node_box (nworld, nodes +
+  nflex, 6) and rc.flexvert_norm (nworld, nflexvert, 3), which `refit_bvh` fills; `render` refuses the context until
+  it has.  flex_render_smooth: cloth faces are offset along the vertex normals (True) or along each element's own
+  normal (False).  rc.flex_bvh_min_faces (a host int the caller may change, default bvh.FLEX_BVH_MIN_FACES; 0 walks
+  every flex): flexes with fewer faces are intersected face by face, with the same image.  For a model without
+  flexes the flag changes nothing.  Without it a model with flexes raises NotImplementedError: its flex elements
+  would be silently invisible.
+
+  Accepted and ignored: `use_textures` (the MJCF compiler keeps no textures, colours are mat_rgba / geom_rgba) and
+  `use_precomputed_rays` (the rays are always made in the kernel, so per-world cam_fovy / cam_intrinsic work)."""
   from .io import _device
 
-  if int(getattr(mjm, "nflex", 0)) > 0:
-    raise NotImplementedError("create_render_context: flex rendering is not part of this build (the model has flexes)")
+  nflex = int(getattr(mjm, "nflex", 0))
+  if nflex > 0 and not render_flex:
+    raise NotImplementedError("create_render_context: flex rendering is opt-in and the model has flexes: pass render_flex=True "
+                              "(call refit_bvh before render)")
   dev = _device(device)
   nworld = int(nworld)
   if nworld < 1:
@@ -124,7 +144,28 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
     node, tri, adr, bvh_depth = build_mesh_bvh(mjm.mesh_vert, mjm.mesh_vertadr, mjm.mesh_face, mjm.mesh_faceadr, mjm.mesh_facenum)
   else:
     node, tri, adr, bvh_depth = build_mesh_bvh(np.zeros((0, 3)), [], np.zeros((0, 3)), [], [])
+  flex = {}
+  if nflex > 0:
+    t = build_flex_tables(mjm, smooth=bool(flex_render_smooth))
+    nnode, nfv = int(t["node"].shape[0]), int(mjm.nflexvert)
+    rgba = np.asarray(getattr(mjm, "flex_rgba", np.tile([0.5, 0.5, 0.5, 1.0], (nflex, 1))), dtype=np.float32).reshape(nflex, 4)
+    f32 = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float32)), device=dev)
+    flex = dict(
+      render_flex=True,
+      flex_render_smooth=bool(flex_render_smooth),
+      flex_info=i32(t["info"]), flex_corner=i32(t["corner"]), flex_elem_vert=i32(t["elem_vert"]), flex_edge_vert=i32(t["edge_vert"]),
+      flex_inc_adr=i32(t["inc_adr"]), flex_inc=i32(t["inc"]), flex_bvh_node=torch.as_tensor(t["node"], device=dev),
+      flex_bvh_tri=i32(t["tri"]), flex_bvh_level=i32(t["level"]), flex_radius=f32(mjm.flex_radius), flex_rgba=f32(rgba),
+      flex_node_box=torch.zeros((nworld, nnode + nflex, 6), dtype=torch.float32, device=dev),
+      flexvert_norm=torch.zeros((nworld, nfv, 3), dtype=torch.float32, device=dev),
+      flex_bvh_max_depth=int(t["depth"]),
+      flex_bvh_min_faces=FLEX_BVH_MIN_FACES,
+      _flex_frag=[np.asarray(x) for x in t["frag"]],
+      _flex_counts=(nflex, nfv, int(mjm.nflexelem), int(mjm.nflexedge)),
+      _flex_refit=False,
+    )
   return RenderContext(
+    **flex,
     nworld=nworld,
     nrender=ncam,
     cam_res=i32(res.reshape(ncam, 2)),
@@ -218,6 +259,51 @@ def _cbvh(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CBvh:
   return c
 
 
+_FLEX_TABLES = (("info", "flex_info", torch.int32, (FLEX_INFO_WORDS,)), ("flex_radius", "flex_radius", torch.float32, ()),
+                ("flex_rgba", "flex_rgba", torch.float32, (4,)), ("corner", "flex_corner", torch.int32, (3, 3)),
+                ("elem_vert", "flex_elem_vert", torch.int32, (3,)), ("edge_vert", "flex_edge_vert", torch.int32, (2,)),
+                ("inc_adr", "flex_inc_adr", torch.int32, ()), ("inc", "flex_inc", torch.int32, ()), ("node", "flex_bvh_node", torch.float32, (NODE_WORDS,)),
+                ("tri", "flex_bvh_tri", torch.int32, ()), ("level", "flex_bvh_level", torch.int32, ()))
+
+
+def _is_flex(rc: RenderContext) -> bool:
+  return bool(getattr(rc, "render_flex", False))
+
+
+def _cflex(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CFlexRender:
+  """mjw_flexrender_t of a context made with render_flex; ValueError when it was made for another model or nworld,
+  or when a table has not the shape its counts ask for (the kernels trust the counts)."""
+  nflex, nfv, nelem, nedge = rc._flex_counts
+  if (nflex, nfv, nelem, nedge) != (int(m.nflex), int(m.nflexvert), int(m.nflexelem), int(m.nflexedge)):
+    raise ValueError(f"{who}: the render context was made for a model with {nflex} flexes, {nfv} flex vertices, {nelem} elements and {nedge} edges, "
+                     f"this one has {m.nflex}, {m.nflexvert}, {m.nflexelem} and {m.nflexedge}")
+  if int(rc.nworld) != int(d.nworld):
+    raise ValueError(f"{who}: the render context was made for nworld = {rc.nworld}, the Data has {d.nworld}")
+  dev = d.qpos.device
+  c = _lib.CFlexRender()
+  for cname, name, dtype, tail in _FLEX_TABLES:
+    t = getattr(rc, name)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape[1:]) != tail:
+      raise ValueError(f"{who}: rc.{name} must be a contiguous {dtype} tensor of shape (n, {tail}) on {dev}")
+    setattr(c, cname, t.data_ptr())
+  nface, nnode = int(rc.flex_corner.shape[0]), int(rc.flex_bvh_node.shape[0])
+  want = dict(flex_info=nflex, flex_radius=nflex, flex_rgba=nflex, flex_elem_vert=nelem, flex_edge_vert=nedge, flex_inc_adr=nfv + 1, flex_bvh_tri=nface)
+  for name, n in want.items():
+    if int(getattr(rc, name).shape[0]) != n:
+      raise ValueError(f"{who}: rc.{name} must hold {n} rows")
+  for name, shape in (("flex_node_box", (int(rc.nworld), nnode + nflex, 6)), ("flexvert_norm", (int(rc.nworld), nfv, 3))):
+    t = getattr(rc, name)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
+      raise ValueError(f"{who}: rc.{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+  if int(rc.flex_bvh_max_depth) > BVH_MAX_DEPTH:
+    raise ValueError(f"{who}: the context's flex trees have {rc.flex_bvh_max_depth} levels; the kernel takes {BVH_MAX_DEPTH}")
+  c.nflex, c.nflexvert, c.nflexelem, c.nflexedge, c.nface, c.nnode = nflex, nfv, nelem, nedge, nface, nnode
+  c.ninc, c.nlevel = int(rc.flex_inc.shape[0]), int(rc.flex_bvh_level.shape[0])
+  c.leaf_size, c.max_depth, c.min_faces = BVH_LEAF, int(rc.flex_bvh_max_depth), max(int(rc.flex_bvh_min_faces), 0)
+  c.node_box, c.vert_norm = rc.flex_node_box.data_ptr(), rc.flexvert_norm.data_ptr()
+  return c
+
+
 def render(m: Model, d: Data, rc: RenderContext) -> None:
   """Renders every camera of the context in every world into rc.rgb_data / rc.depth_data / rc.seg_data
   (render.py:515-830), in one launch on the Data's stream; capturable in a graph.
@@ -230,7 +316,12 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   and mat_rgba may be batched per world.  The camera, light and geom frames are those of the last position
   stage (`forward`, `step`, `kinematics` + `camlight`).  Meshes are walked through the context's BVHs; with a
   per-world batched `m.mesh_vert` (leading dim > 1), which the trees were not built from, the launch loops over
-  every face instead.  Both give the same images bit for bit."""
+  every face instead.  Both give the same images bit for bit.
+
+  A context made with render_flex also draws the flexes, from the boxes and normals the last `refit_bvh` left (it does
+  not refit; before the first `refit_bvh` it raises ValueError): the nearest hit over geoms and flexes, a flex only
+  when strictly nearer than every geom; segmentation -2, colour flex_rgba (no material, texture or group filter), the
+  normal of a flex triangle its winding normal turned to face the ray; flexes throw and receive shadows like geoms."""
   if not isinstance(rc, RenderContext):
     raise ValueError("render: rc must be a RenderContext from create_render_context")
   dev = d.qpos.device
@@ -248,6 +339,15 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   bvh = _cbvh(rc, m, d, "render")
   rm = _ray_model(m)
   c = _crender(rc)
+  if _is_flex(rc):
+    fr = _cflex(rc, m, d, "render")
+    if not rc._flex_refit:
+      raise ValueError("render: the context's flex trees have never been refit: call refit_bvh(m, d, rc) after the step and before render")
+    if c.ntile == 0:
+      return
+    rcode = _lib.lib().mjw_render_flex(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), ctypes.byref(fr), _stream(d))
+    _lib.check(rcode, "mjw_render_flex")
+    return
   if c.ntile == 0:
     return
   rcode = _lib.lib().mjw_render_bvh(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), _stream(d))
@@ -255,9 +355,23 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
 
 
 def refit_bvh(m: Model, d: Data, rc: RenderContext) -> None:
-  """Does nothing.  The only BVHs are the per-mesh trees of the context, which live in each mesh's own frame:
-  meshes are rigid, so a moving geom moves its frame and the tree stays valid.  There is no BVH over the geoms to
-  refit.  It exists so that code written for the reference (`refit_bvh` before every `render`) runs unchanged."""
+  """Refits the flex trees of a context made with render_flex to `d.flexvert_xpos`: one launch (`mjw_flex_refit`) on
+  the Data's stream writes, per world, the vertex normals, every node's box and the whole-flex boxes; capturable in a
+  graph.  Call it after the step (or `forward`) and before `render`, once per step.
+
+  For every other context it does nothing.  The per-mesh trees live in each mesh's own frame: meshes are rigid, so a
+  moving geom moves its frame and the tree stays valid, and there is no BVH over the geoms to refit.  So code written
+  for the reference (`refit_bvh` before every `render`) runs unchanged.  Returns None either way."""
+  if not isinstance(rc, RenderContext) or not _is_flex(rc):
+    return None
+  from .forward import _stream
+  from .io import cdata, cmodel
+
+  fr = _cflex(rc, m, d, "refit_bvh")
+  rcode = _lib.lib().mjw_flex_refit(cmodel(m), cdata(d), ctypes.byref(fr), _stream(d))
+  _lib.check(rcode, "mjw_flex_refit")
+  rc._flex_refit = True
+  return None
 
 
 def _view(rc, camera_index, which, out, shape_tail, dtype, name):

@@ -409,7 +409,13 @@ class RenderContext(_Container):
   (nmesh, 4) int32, empty for a model without meshes; bvh_leaf_size and bvh_max_depth are host ints.  `render` and
   `rays(rc=...)` walk them for the meshes of at least bvh_min_faces faces (a host int, default bvh.BVH_MIN_FACES; set
   it to 0 to walk every mesh) and loop over the faces of the smaller ones, with the same results either way.
-  There is no BVH over the geoms, no texture and no flex state."""
+  There is no BVH over the geoms and no texture.
+
+  A context made with render_flex=True also holds the flex tables (bvh.py `build_flex_tables`: flex_info, flex_corner,
+  flex_elem_vert, flex_edge_vert, flex_inc_adr, flex_inc, flex_bvh_node, flex_bvh_tri, flex_bvh_level, flex_radius,
+  flex_rgba), the per-world buffers flex_node_box (nworld, nodes + nflex, 6) and flexvert_norm (nworld, nflexvert, 3)
+  that `refit_bvh` fills, and the host ints flex_bvh_max_depth and flex_bvh_min_faces (flexes with fewer faces are
+  intersected face by face; 0 walks every flex).  Other contexts have none of these fields."""
 
 
 class Contact(_Container):
