@@ -19,9 +19,10 @@
  *   mjw_sensor            <- sensor.sensor_pos/_vel/_acc  sensor.py:761,1377,2447
  *   mjw_ctrl_noise        <- benchmark.ctrl_noise         _src/benchmark.py:41-83
  *   mjw_rays              <- ray.rays (no render context) ray.py:1212-1312
- *   mjw_render            <- render.render (brute force over the geoms; no textures) render.py:515-830
+ *   mjw_render            <- render.render (brute force over the geoms; textures: mjw_render_tex) render.py:515-830
  *   mjw_rays_bvh / mjw_render_bvh <- the same with a static BVH per mesh (no BVH over the geoms, none to refit)
  *   mjw_flex_refit / mjw_render_flex <- render.refit_bvh / render.render of a context made with render_flex
+ *   mjw_render_tex        <- render.render of a context that has textures (use_textures; planes and meshes with texcoords)
  *   mjw_inverse           <- inverse.inverse's constraint + combine  inverse.py, solver.py init_context(grad=False)
  *   mjw_island            <- island.island (connected components by union-find, no tree x tree matrix) island.py:246-265
  *
@@ -531,6 +532,45 @@ int mjw_flex_refit(const mjw_model_t* m, const mjw_data_t* d, const mjw_flexrend
  * is mjw_render_bvh / mjw_render.  Errors as those calls and mjw_flex_refit. */
 int mjw_render_flex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
                     const mjw_flexrender_t* fr, void* stream);
+
+/* Textured rendering (mjw_render_tex): the 2D textures of a render context made with use_textures, the materials'
+ * texture ids and repeats (per world: world w reads row w % nb) and the meshes' texture coordinates.  It stays out
+ * of mjw_model_t / mjw_render_t like mjw_flexrender_t; every pointer is a device pointer.  tex_data: one word per
+ * texel, r | g << 8 | b << 16 | 255 << 24, row y of a texture is v; tex_adr: the first word of each texture, -1 for
+ * one that is never sampled (cube, skybox, no data).  mesh_facetexcoord indexes mesh_texcoord relative to
+ * mesh_texcoordadr[mesh], which is -1 for a mesh without texture coordinates.  The kernel treats every id or
+ * address outside its table as "no texture": a table that does not fit samples nothing and nothing outside it is read. */
+typedef struct mjw_texture_t {
+  int32_t ntex;              /* textures: entries of tex_adr / tex_width / tex_height */
+  int32_t ntexdata;          /* words of tex_data */
+  int32_t nmat;              /* must equal mjw_ray_model_t.nmat */
+  int32_t nmesh;             /* entries of mesh_texcoordadr: the model's nmesh, or 0 */
+  int32_t ntexcoord;         /* rows of mesh_texcoord */
+  int32_t nmeshface;         /* rows of mesh_facetexcoord: mjw_ray_model_t.nmeshface, or 0 */
+  int32_t mat_texid_nb;      /* >= 1 */
+  int32_t mat_texrepeat_nb;  /* >= 1 */
+  const int32_t* mat_texid;         /* (mat_texid_nb, nmat, 10): texture id per role; only role 1 (RGB) is read */
+  const float* mat_texrepeat;       /* (mat_texrepeat_nb, nmat, 2) */
+  const int32_t* tex_data;          /* (ntexdata,) */
+  const int32_t* tex_adr;           /* (ntex,) */
+  const int32_t* tex_width;         /* (ntex,) */
+  const int32_t* tex_height;        /* (ntex,) */
+  const float* mesh_texcoord;       /* (ntexcoord, 2) */
+  const int32_t* mesh_texcoordadr;  /* (nmesh,) */
+  const int32_t* mesh_facetexcoord; /* (nmeshface, 3) */
+} mjw_texture_t;
+int mjw_sizeof_texture(void);
+/* mjw_render_flex (fr != NULL), mjw_render_bvh (fr == NULL, bvh != NULL) or mjw_render (both NULL) with the base
+ * colour of every geom pixel multiplied, before the ambient and light terms, by a bilinear sample of the texture
+ * that role 1 of the geom's material names, where the geom is a plane (uv = the hit in the geom's frame, x and y)
+ * or a mesh whose mesh has texture coordinates (uv = the barycentric mean of the hit face's three; the face is the
+ * nearest, the lowest id among equal distances).  s = frac(uv * texrepeat); the four texels around (s.x W - 0.5,
+ * s.y H - 0.5) are blended with float32 weights, indices taken modulo W and H.  Every other geom, a mesh without
+ * texture coordinates and every flex keep their colour; depth and segmentation are those of the call without
+ * textures.  With ntex, ntexdata or nmat zero it is that call.  Errors as those calls; a null tex or a null table
+ * with a non-zero count gives -1, a negative count, a batch size under 1 or counts that differ from the model's -4. */
+int mjw_render_tex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
+                   const mjw_flexrender_t* fr, const mjw_texture_t* tex, void* stream);
 
 #ifdef __cplusplus
 }

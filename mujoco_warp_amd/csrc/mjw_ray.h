@@ -539,7 +539,8 @@ struct MeshSrc {
 
 template <bool ANYHIT, class Src>
 __device__ __forceinline__ float bvh_walk(const Src& src, const float* nodes, int nnode, const int* tri, int nface, bool cand,
-                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl) {
+                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl,
+                                          int* face = nullptr) {
   float x = -1.0f;
   RaySlab slab;
   ray_slab(lv, slab);
@@ -600,18 +601,21 @@ __device__ __forceinline__ float bvh_walk(const Src& src, const float* nodes, in
     sp--;
     node = uni(__builtin_amdgcn_readlane(stack, sp));
   }
+  if (face) *face = x >= 0.0f ? bf : -1;  // (textured shading asks which face; every other caller passes none)
   return x;
 }
 
 template <bool ANYHIT>
 __device__ __forceinline__ float mesh_bvh(const BvhArgs& bv, int mesh, const float* vert, const int* face, int nface, bool cand,
-                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl) {
+                                          const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl,
+                                          int* face_out = nullptr) {
+  if (face_out) *face_out = -1;
   if (mesh >= bv.nmesh) return -1.0f;  // (uniform, like every test of the tables below: a table that does not fit hits nothing)
   const int* adr = bv.adr + 4 * (long)mesh;
   const int nadr = uni(adr[0]), nnode = uni(adr[1]), triadr = uni(adr[2]);
   if (nadr < 0 || nnode < 1 || nadr > bv.nnode - nnode || triadr < 0 || triadr > bv.ntri - nface) return -1.0f;  // (uniform)
   const float* nodes = bv.node + 8 * (long)nadr;
-  return bvh_walk<ANYHIT>(MeshSrc{nodes, vert, face}, nodes, nnode, bv.tri + triadr, nface, cand, lp, lv, b0, b1, best, nl);
+  return bvh_walk<ANYHIT>(MeshSrc{nodes, vert, face}, nodes, nnode, bv.tri + triadr, nface, cand, lp, lv, b0, b1, best, nl, face_out);
 }
 
 // Every lane's ray (pnt, vec; world frame) against the n staged geoms g0 ..: a hit nearer than `best` (strict

@@ -68,8 +68,157 @@ __device__ __forceinline__ void pixel_ray(float fovy, const float* sensorsize, c
   normalize3(local);
 }
 
-template <int NT, bool BVH, bool FLEX>
-__device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& bv, const FlexArgs& fx, float* recs) {
+// ---- textures (mjw_render_tex; TEX = true) ---------------------------------------------------------------------------
+//
+// The base colour of a pixel on a plane, or on a mesh that has texture coordinates, is multiplied by a bilinear sample
+// of the 2D texture its material names in role 1 (render.py:43-84 `sample_texture`, 694-717).  The tables are those
+// of mjw_texture_t; an id or address outside its table means "no texture", so a table that does not fit samples nothing.
+struct TexArgs {
+  int ntex, ntexdata, nmat, nmesh, ntexcoord, nmeshface, texid_nb, texrep_nb;
+  const int* mat_texid;        // (texid_nb, nmat, 10)
+  const float* mat_texrepeat;  // (texrep_nb, nmat, 2)
+  const int *tex_data, *tex_adr, *tex_width, *tex_height;
+  const float* mesh_texcoord;
+  const int *mesh_texcoordadr, *mesh_facetexcoord;
+};
+
+// the texel (x, y) of a texture as three floats in [0, 1]; x, y already inside the texture
+__device__ __forceinline__ void texel(const int* data, int W, int x, int y, float* c) {
+  const unsigned w = (unsigned)data[(long)y * W + x];
+  c[0] = (float)(w & 255u) * (1.0f / 255.0f);
+  c[1] = (float)((w >> 8) & 255u) * (1.0f / 255.0f);
+  c[2] = (float)((w >> 16) & 255u) * (1.0f / 255.0f);
+}
+
+// bilinear sample with repeat addressing: s = frac(uv * repeat), texel centres at (i + 0.5) / W, fp32 weights
+__device__ __forceinline__ void tex_sample(const int* data, int W, int H, const float* uv, const float* rep, float* c) {
+  float s0 = uv[0] * rep[0], s1 = uv[1] * rep[1];
+  s0 -= floorf(s0);
+  s1 -= floorf(s1);
+  const float x = s0 * (float)W - 0.5f, y = s1 * (float)H - 0.5f;
+  // floor(x) lies in -1 .. W - 1; the clamp also catches a uv that is not finite
+  const float xf = fminf(fmaxf(floorf(x), -1.0f), (float)(W - 1)), yf = fminf(fmaxf(floorf(y), -1.0f), (float)(H - 1));
+  float wx = x - xf, wy = y - yf;
+  wx = wx >= 0.0f && wx <= 1.0f ? wx : 0.0f;
+  wy = wy >= 0.0f && wy <= 1.0f ? wy : 0.0f;
+  const int x0 = xf < 0.0f ? W - 1 : (int)xf, y0 = yf < 0.0f ? H - 1 : (int)yf;
+  const int x1 = x0 + 1 < W ? x0 + 1 : 0, y1 = y0 + 1 < H ? y0 + 1 : 0;
+  float t00[3], t10[3], t01[3], t11[3];
+  texel(data, W, x0, y0, t00);
+  texel(data, W, x1, y0, t10);
+  texel(data, W, x0, y1, t01);
+  texel(data, W, x1, y1, t11);
+  for (int i = 0; i < 3; i++)
+    c[i] = (1.0f - wy) * ((1.0f - wx) * t00[i] + wx * t10[i]) + wy * ((1.0f - wx) * t01[i] + wx * t11[i]);
+}
+
+// Multiplies base by the texel colour of the lane's first hit (geom bid at distance best along pnt + x vec) where the
+// rules above give it one.  Every lane of the wave must call it: the face of a mesh hit is found again here, one hit
+// mesh geom of the wave at a time, by the walk or the face loop that found it in trace_chunk (the nearest triangle,
+// the lowest face id among equal distances), so the kernels without textures carry no face id.
+// recs: the staged records of the model's only chunk (ngeom <= RAY_CHUNK: the primary rays left them in LDS), else null.
+template <bool BVH>
+__device__ __forceinline__ void tex_shade(const GeomArgs& g, const BvhArgs& bv, const TexArgs& tx, int wid, const float* recs, bool on, int bid,
+                                          int matid, const float* pnt, const float* vec, float best, float* base) {
+  // the hit geom's type and the ray in its frame, read before the texture's header so that the loads do not queue
+  // behind it: from the staged record where there is one (the floats trace_chunk mapped the ray with), else from the arrays
+  int gtype = -1;
+  float lp[3] = {0.0f, 0.0f, 0.0f}, lv[3] = {0.0f, 0.0f, -1.0f}, uv[2] = {0.0f, 0.0f};
+  if (on && matid >= 0) {
+    if (recs) {
+      const float* rec = recs + bid * RECW;
+      gtype = reinterpret_cast<const int*>(rec)[R_TYPE];
+      ray_map(rec + R_POS, rec + R_MAT, pnt, vec, lp, lv);
+    } else {
+      gtype = g.geom_type[bid];
+      ray_map(g.geom_xpos + ((long)wid * g.ngeom + bid) * 3, g.geom_xmat + ((long)wid * g.ngeom + bid) * 9, pnt, vec, lp, lv);
+    }
+  }
+  int texid = -1;
+  float rep[2] = {1.0f, 1.0f};
+  if (on && matid >= 0 && matid < g.nmat && matid < tx.nmat) {
+    texid = tx.mat_texid[((long)(wid % tx.texid_nb) * tx.nmat + matid) * 10 + 1];
+    const float* r = tx.mat_texrepeat + ((long)(wid % tx.texrep_nb) * tx.nmat + matid) * 2;
+    rep[0] = r[0];
+    rep[1] = r[1];
+  }
+  int adr = -1, W = 0, H = 0;
+  if (texid >= 0 && texid < tx.ntex) {
+    adr = tx.tex_adr[texid];
+    W = tx.tex_width[texid];
+    H = tx.tex_height[texid];
+  }
+  const bool tex = adr >= 0 && W >= 1 && H >= 1 && (long)adr + (long)W * (long)H <= (long)tx.ntexdata;
+  const int type = tex ? gtype : -1;
+  const float hl[3] = {lp[0] + best * lv[0], lp[1] + best * lv[1], lp[2] + best * lv[2]};  // the hit in the geom's frame
+  bool have = type == RG_PLANE;
+  if (have) {
+    uv[0] = hl[0];
+    uv[1] = hl[1];
+  }
+  bool pending = type == RG_MESH;
+  unsigned long long mask;
+  while ((mask = __ballot(pending)) != 0ull) {
+    const int gsel = uni(__builtin_amdgcn_readlane(bid, (int)__ffsll((long long)mask) - 1));
+    const bool mine = pending && bid == gsel;
+    pending = pending && !mine;
+    const int mesh = uni(g.geom_dataid[gsel]);
+    if (mesh < 0 || mesh >= g.nmesh || mesh >= tx.nmesh) continue;
+    const int tadr = uni(tx.mesh_texcoordadr[mesh]);
+    if (tadr < 0) continue;  // a mesh without texcoords keeps its base colour
+    const float* vert = row(g.mesh_vert, g.vert_nb, (long)g.nmeshvert * 3, wid) + 3 * (long)g.mesh_vertadr[mesh];
+    const int f0 = uni(g.mesh_faceadr[mesh]), f1 = min(f0 + uni(g.mesh_facenum[mesh]), g.nmeshface);
+    if (f0 < 0 || f1 < f0) continue;
+    float b0[3], b1[3], nl[3];
+    ray_basis(lv, b0, b1);
+    int face = -1;
+    if (BVH && f1 - f0 >= bv.min_faces) {
+      mesh_bvh<false>(bv, mesh, vert, g.mesh_face + 3 * (long)f0, f1 - f0, mine, lp, lv, b0, b1, MJW_MAXVAL, nl, &face);
+    } else {
+      float x = -1.0f;
+      for (int f = f0; f < f1; f++) {
+        const int* idx = g.mesh_face + 3 * (long)f;
+        const float sol = ray_triangle(vert + 3 * idx[0], vert + 3 * idx[1], vert + 3 * idx[2], lp, lv, b0, b1, nl);
+        if (sol >= 0.0f && (x < 0.0f || sol < x)) {
+          x = sol;
+          face = f - f0;
+        }
+      }
+    }
+    // per lane from here (no `continue`: the loop's ballot needs the whole wave back together)
+    if (mine && face >= 0 && face < f1 - f0 && f0 + face < tx.nmeshface) {
+      const int* idx = g.mesh_face + 3 * (long)(f0 + face);
+      const int* ti = tx.mesh_facetexcoord + 3 * (long)(f0 + face);
+      const long t0 = (long)tadr + ti[0], t1 = (long)tadr + ti[1], t2 = (long)tadr + ti[2];
+      if (ti[0] >= 0 && ti[1] >= 0 && ti[2] >= 0 && t0 < tx.ntexcoord && t1 < tx.ntexcoord && t2 < tx.ntexcoord) {
+        const float *v0 = vert + 3 * idx[0], *v1 = vert + 3 * idx[1], *v2 = vert + 3 * idx[2];
+        const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+        const float d0[3] = {v0[0] - hl[0], v0[1] - hl[1], v0[2] - hl[2]}, d1[3] = {v1[0] - hl[0], v1[1] - hl[1], v1[2] - hl[2]};
+        const float d2[3] = {v2[0] - hl[0], v2[1] - hl[1], v2[2] - hl[2]};
+        float n[3], c0[3], c1[3];
+        cross3(n, e1, e2);
+        const float nn = dot3(n, n);
+        if (nn > 0.0f) {  // barycentrics of the hit: signed sub-triangle areas over the triangle's
+          cross3(c0, d1, d2);
+          cross3(c1, d2, d0);
+          const float w0 = dot3(n, c0) / nn, w1 = dot3(n, c1) / nn, w2 = 1.0f - w0 - w1;
+          const float *u0 = tx.mesh_texcoord + 2 * t0, *u1 = tx.mesh_texcoord + 2 * t1, *u2 = tx.mesh_texcoord + 2 * t2;
+          uv[0] = w0 * u0[0] + w1 * u1[0] + w2 * u2[0];
+          uv[1] = w0 * u0[1] + w1 * u1[1] + w2 * u2[1];
+          have = true;
+        }
+      }
+    }
+  }
+  if (have) {
+    float c[3];
+    tex_sample(tx.tex_data + adr, W, H, uv, rep, c);
+    for (int i = 0; i < 3; i++) base[i] *= c[i];
+  }
+}
+
+template <int NT, bool BVH, bool FLEX, bool TEX = false>
+__device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& bv, const FlexArgs& fx, float* recs, const TexArgs* tx = nullptr) {
   const int tid = threadIdx.x;
   const int wid = blockIdx.x / a.ntile, t = blockIdx.x - wid * a.ntile;
   const int ci = a.tile[4 * t], x0 = a.tile[4 * t + 1], y0 = a.tile[4 * t + 2];
@@ -125,6 +274,7 @@ __device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& 
   } else if (bid >= 0) {
     for (int i = 0; i < 3; i++) base[i] = col[i];
   }
+  if (TEX) tex_shade<BVH>(a.g, bv, *tx, wid, a.g.ngeom <= RAY_CHUNK ? recs : nullptr, active && bid >= 0 && fid < 0, bid, matid, pnt, vec, best, base);
   const float hp[3] = {pnt[0] + vec[0] * best, pnt[1] + vec[1] * best, pnt[2] + vec[2] * best};
   float n[3] = {bn[0], bn[1], bn[2]};
   if (!(dot3(n, n) > 0.0f)) { n[0] = 0.0f; n[1] = 0.0f; n[2] = 1.0f; }
@@ -204,13 +354,54 @@ __global__ void __launch_bounds__(NT) render_flex_kernel(const RenderArgs a, con
   render_body<NT, BVH, true>(a, bv, fx, recs);
 }
 
+// the same with textures (TexArgs), with or without the BVHs and the flexes
+template <int NT, bool BVH, bool FLEX>
+__global__ void __launch_bounds__(NT) render_tex_kernel(const RenderArgs a, const BvhArgs bv, const FlexArgs fx, const TexArgs tx) {
+  __shared__ float recs[RAY_CHUNK * RECW];
+  render_body<NT, BVH, FLEX, true>(a, bv, fx, recs, &tx);
+}
+
+// host: the checks of mjw_texture_t; 1: sample, 0: nothing to sample (the call is the one without textures), < 0: refused
+static int check_tex_args(const mjw_model_t* m, const mjw_ray_model_t* rm, const mjw_texture_t* t, TexArgs& tx) {
+  if (!t) return set_last_error(-1, "mjw_render_tex: null texture tables");
+  if (t->ntex < 0 || t->ntexdata < 0 || t->nmat < 0 || t->nmesh < 0 || t->ntexcoord < 0 || t->nmeshface < 0)
+    return set_last_error(-4, "mjw_render_tex: negative count");
+  if (t->mat_texid_nb < 1 || t->mat_texrepeat_nb < 1) return set_last_error(-4, "mjw_render_tex: mat_texid / mat_texrepeat batch size < 1");
+  if (t->nmat != rm->nmat) return set_last_error(-4, "mjw_render_tex: nmat differs from the ray model's");
+  if ((t->nmesh != 0 && t->nmesh != m->nmesh) || (t->nmeshface != 0 && t->nmeshface != rm->nmeshface))
+    return set_last_error(-4, "mjw_render_tex: nmesh / nmeshface differ from the model's");
+  if (t->nmat > 0 && (!t->mat_texid || !t->mat_texrepeat)) return set_last_error(-1, "mjw_render_tex: null mat_texid / mat_texrepeat");
+  if (t->ntex > 0 && (!t->tex_adr || !t->tex_width || !t->tex_height)) return set_last_error(-1, "mjw_render_tex: null texture table");
+  if (t->ntexdata > 0 && !t->tex_data) return set_last_error(-1, "mjw_render_tex: null tex_data");
+  if ((t->nmesh > 0 && !t->mesh_texcoordadr) || (t->ntexcoord > 0 && !t->mesh_texcoord) || (t->nmeshface > 0 && !t->mesh_facetexcoord))
+    return set_last_error(-1, "mjw_render_tex: null texcoord table");
+  if (t->ntex == 0 || t->ntexdata == 0 || t->nmat == 0) return 0;
+  tx.ntex = t->ntex; tx.ntexdata = t->ntexdata; tx.nmat = t->nmat; tx.nmesh = t->nmesh; tx.ntexcoord = t->ntexcoord; tx.nmeshface = t->nmeshface;
+  tx.texid_nb = t->mat_texid_nb; tx.texrep_nb = t->mat_texrepeat_nb;
+  tx.mat_texid = t->mat_texid; tx.mat_texrepeat = t->mat_texrepeat;
+  tx.tex_data = t->tex_data; tx.tex_adr = t->tex_adr; tx.tex_width = t->tex_width; tx.tex_height = t->tex_height;
+  tx.mesh_texcoord = t->mesh_texcoord; tx.mesh_texcoordadr = t->mesh_texcoordadr; tx.mesh_facetexcoord = t->mesh_facetexcoord;
+  return 1;
+}
+
 }  // namespace ray
 }  // namespace mjw
 
+template <int NT, bool BVH, bool FLEX>
+static void launch_tex(long nblock, hipStream_t s, const mjw::ray::RenderArgs& a, const mjw::ray::BvhArgs& bv, const mjw::ray::FlexArgs& fx,
+                       const mjw::ray::TexArgs& tx) {
+  hipLaunchKernelGGL((mjw::ray::render_tex_kernel<NT, BVH, FLEX>), dim3((unsigned)nblock), dim3(NT), 0, s, a, bv, fx, tx);
+}
+
 static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
-                         bool with_bvh, const mjw_flexrender_t* fr, bool with_flex, void* stream) {
+                         bool with_bvh, const mjw_flexrender_t* fr, bool with_flex, void* stream, const mjw_texture_t* tex = nullptr,
+                         bool with_tex = false) {
   using namespace mjw::ray;
   if (!m || !d || !rm || !rc) return mjw::set_last_error(-1, "mjw_render: null model / data / ray model / render context");
+  TexArgs tx;
+  memset(&tx, 0, sizeof(tx));
+  int textured = 0;
+  if (with_tex && (textured = check_tex_args(m, rm, tex, tx)) < 0) return textured;
   BvhArgs bv;
   memset(&bv, 0, sizeof(bv));
   int walk = 0;
@@ -253,7 +444,19 @@ static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ra
   hipStream_t s = (hipStream_t)stream;
   const long nblock = (long)a.nworld * a.ntile;
   if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, "mjw_render: nworld x tiles exceeds the grid limit");
-  if (flex) {
+  if (textured) {
+    const int k = (rc->tile_threads == 64 ? 4 : 0) | (walk ? 2 : 0) | (flex ? 1 : 0);
+    switch (k) {
+      case 0: launch_tex<256, false, false>(nblock, s, a, bv, fx, tx); break;
+      case 1: launch_tex<256, false, true>(nblock, s, a, bv, fx, tx); break;
+      case 2: launch_tex<256, true, false>(nblock, s, a, bv, fx, tx); break;
+      case 3: launch_tex<256, true, true>(nblock, s, a, bv, fx, tx); break;
+      case 4: launch_tex<64, false, false>(nblock, s, a, bv, fx, tx); break;
+      case 5: launch_tex<64, false, true>(nblock, s, a, bv, fx, tx); break;
+      case 6: launch_tex<64, true, false>(nblock, s, a, bv, fx, tx); break;
+      default: launch_tex<64, true, true>(nblock, s, a, bv, fx, tx); break;
+    }
+  } else if (flex) {
     const bool small = rc->tile_threads == 64;
     if (walk && small) hipLaunchKernelGGL((render_flex_kernel<64, true>), dim3((unsigned)nblock), dim3(64), 0, s, a, bv, fx);
     else if (walk) hipLaunchKernelGGL((render_flex_kernel<256, true>), dim3((unsigned)nblock), dim3(256), 0, s, a, bv, fx);
@@ -286,4 +489,11 @@ extern "C" int mjw_render_bvh(const mjw_model_t* m, const mjw_data_t* d, const m
 extern "C" int mjw_render_flex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc,
                                const mjw_bvh_t* bvh, const mjw_flexrender_t* fr, void* stream) {
   return render_launch(m, d, rm, rc, bvh, bvh != nullptr, fr, true, stream);
+}
+
+extern "C" int mjw_sizeof_texture(void) { return (int)sizeof(mjw_texture_t); }
+
+extern "C" int mjw_render_tex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
+                              const mjw_flexrender_t* fr, const mjw_texture_t* tex, void* stream) {
+  return render_launch(m, d, rm, rc, bvh, bvh != nullptr, fr, fr != nullptr, stream, tex, true);
 }

@@ -482,6 +482,9 @@ def put_model(mjm, device=None) -> types.Model:
   m.geom_matid = _i32(np.asarray(getattr(mjm, "geom_matid", -np.ones(ng))).reshape(-1)[:ng], dev)
   m.geom_rgba = _f32(np.asarray(getattr(mjm, "geom_rgba", np.tile([0.5, 0.5, 0.5, 1.0], (ng, 1))), dtype=np.float64).reshape(1, ng, 4), dev)
   m.mat_rgba = _f32(np.asarray(getattr(mjm, "mat_rgba", np.zeros((0, 4))), dtype=np.float64).reshape(1, m.nmat, 4), dev)
+  # textured rendering: each material's texture ids by role (only role 1, RGB, is read) and its repeat; batchable per world
+  m.mat_texid = _i32(np.asarray(getattr(mjm, "mat_texid", -np.ones((m.nmat, 10)))).reshape(1, m.nmat, 10), dev)
+  m.mat_texrepeat = _f32(np.asarray(getattr(mjm, "mat_texrepeat", np.ones((m.nmat, 2))), dtype=np.float64).reshape(1, m.nmat, 2), dev)
   m.mesh_face = _i32(np.asarray(getattr(mjm, "mesh_face", np.zeros((0, 3)))).reshape(m.nmeshface, 3), dev)
   m.mesh_faceadr = _i32(np.asarray(getattr(mjm, "mesh_faceadr", np.zeros(0))), dev)
   m.mesh_facenum = _i32(np.asarray(getattr(mjm, "mesh_facenum", np.zeros(0))), dev)

@@ -396,6 +396,7 @@ class _Compiler:
     self.autolimits = True
     self.inertiafromgeom = "auto"
     self.meshdir = ""
+    self.texturedir = ""
     self.boundmass = 0.0
     self.boundinertia = 0.0
     self.defaults = {}
@@ -695,6 +696,7 @@ class _Compiler:
       self.autolimits = comp.get("autolimits", "true") == "true"
       self.inertiafromgeom = comp.get("inertiafromgeom", "auto")
       self.meshdir = comp.get("meshdir", "")
+      self.texturedir = comp.get("texturedir", comp.get("assetdir", ""))
       self.boundmass = float(comp.get("boundmass", 0.0))
       self.boundinertia = float(comp.get("boundinertia", 0.0))
 
@@ -999,6 +1001,7 @@ class _Compiler:
 
     self._load_meshes(root)
     self._load_hfields(root)
+    self._load_textures(root)
     self._load_materials(root)
     self._build_geoms()
     self._build_inertia()
@@ -1023,14 +1026,21 @@ class _Compiler:
     m = self.m
     self.mesh_id = {}
     self.mesh_data = []  # (vertices (n, 3) float64, triangles (t, 3) int)
+    mesh_tex = []  # per mesh: (texcoords (k, 2), per-face texcoord indices (t, 3)) or None
     for asset in root.findall("asset"):
       for me in asset.findall("mesh"):
         a = self._resolve("mesh", me, None)
         if "file" in a:
-          v, f = _read_mesh_file(os.path.join(self.basedir, self.meshdir, a["file"]))
+          v, f, tc, ftc = _read_mesh_file(os.path.join(self.basedir, self.meshdir, a["file"]), texcoord=True)
         elif "vertex" in a:  # inline mesh: vertices, faces given or the convex hull (MuJoCo user_mesh.cc)
           v = np.array(_floats(a["vertex"]), dtype=np.float64).reshape(-1, 3)
           f = np.array(_floats(a["face"]), dtype=np.int64).reshape(-1, 3) if "face" in a else _hull_faces(v)
+          tc, ftc = None, None
+          if "texcoord" in a:  # one uv per vertex as given: the face's texcoord indices are its vertex indices before the remap
+            tc = np.array(_floats(a["texcoord"]), dtype=np.float64).reshape(-1, 2)
+            if len(tc) != len(v):
+              raise ValueError(f"mesh {a.get('name', '')}: texcoord needs one uv per vertex ({len(v)}), got {len(tc)}")
+            ftc = np.asarray(f, dtype=np.int64).reshape(-1, 3).copy()
         else:
           raise NotImplementedError("<mesh> needs a file or inline vertices")
         v = v * np.array(_merge_vec([1.0, 1.0, 1.0], _floats(a.get("scale", "1 1 1"))))
@@ -1043,6 +1053,7 @@ class _Compiler:
         name = a.get("name") or os.path.splitext(os.path.basename(a.get("file", "")))[0]
         self.mesh_id[name] = len(self.mesh_data)
         self.mesh_data.append((v, f))
+        mesh_tex.append(None if tc is None or len(f) == 0 else (tc, ftc))
     m.nmesh = len(self.mesh_data)
     m.mesh_vertnum = np.array([len(v) for v, _ in self.mesh_data], dtype=np.int32)
     m.mesh_vertadr = np.concatenate([[0], np.cumsum(m.mesh_vertnum)[:-1]]).astype(np.int32) if m.nmesh else np.zeros(0, np.int32)
@@ -1053,6 +1064,16 @@ class _Compiler:
     m.mesh_faceadr = np.concatenate([[0], np.cumsum(m.mesh_facenum)[:-1]]).astype(np.int32) if m.nmesh else np.zeros(0, np.int32)
     m.mesh_face = (np.concatenate([np.asarray(f).reshape(-1, 3) for _, f in self.mesh_data]) if m.nmesh else np.zeros((0, 3))).astype(np.int32)
     m.nmeshface = int(m.mesh_facenum.sum())
+    # texture coordinates (MuJoCo's mesh_texcoord*): per mesh its uv list and, per face, three indices into it (local to
+    # the mesh; they are not vertex indices and the duplicate-vertex remap leaves them alone); texcoordadr -1: none
+    m.mesh_texcoordnum = np.array([0 if t is None else len(t[0]) for t in mesh_tex], dtype=np.int32)
+    adr = np.concatenate([[0], np.cumsum(m.mesh_texcoordnum)[:-1]]).astype(np.int32) if m.nmesh else np.zeros(0, np.int32)
+    m.mesh_texcoordadr = np.where(m.mesh_texcoordnum > 0, adr, -1).astype(np.int32)
+    m.mesh_texcoord = np.concatenate([np.zeros((0, 2))] + [t[0] for t in mesh_tex if t is not None]).reshape(-1, 2)
+    m.ntexcoord = int(m.mesh_texcoordnum.sum())
+    m.mesh_facetexcoord = np.concatenate([np.zeros((0, 3), dtype=np.int64)] + [
+      np.zeros((len(f), 3), dtype=np.int64) if t is None else np.asarray(t[1], dtype=np.int64).reshape(-1, 3)
+      for (_, f), t in zip(self.mesh_data, mesh_tex)]).astype(np.int32)
     # per-vertex normals (MuJoCo's mesh_normal without tangent frames: normalnum = vertnum): the
     # area-weighted mean of the adjacent triangles' normals, in the mesh frame (mesh_quat identity: this
     # compiler keeps mesh vertices in their file frame)
@@ -1076,19 +1097,110 @@ class _Compiler:
     m.mesh_polymap = np.array([i for mp in pmaps for i in mp], dtype=np.int32)
     m.nmeshpoly, m.nmeshpolyvert, m.nmeshpolymap = len(loops), len(m.mesh_polyvert), len(m.mesh_polymap)
 
+  def _load_textures(self, root):
+    """<asset><texture>: MuJoCo's tex_* fields.  Only 2D textures get data (3 channels, uint8, rows top to bottom
+    in file order, byte = floor(c * 255 + 0.5)); cube and skybox textures are recorded with their type and tex_adr -1
+    and are never sampled.  Data of a 2D texture: a PNG file (8 / 16 bit by the high byte, grey replicated, alpha
+    dropped, hflip / vflip honoured) or a builtin: checker (texel (r, c) is rgb1 where (r < height // 2) == (c <
+    width // 2), else rgb2), flat (rgb1), gradient (this build's rule: row r is rgb1 + (rgb2 - rgb1) r / max(height -
+    1, 1)); then mark edge (the outer texel ring) or cross (the middle row and column) in markrgb.  `random` and
+    mark="random" add no noise.  A 2D file of another type is remembered and refused only when a material uses it."""
+    m = self.m
+    self.tex_id, self.tex_refused = {}, {}
+    ttype, width, height, adr, data, names = [], [], [], [], [], []
+    byte = lambda c: np.floor(np.clip(np.asarray(c, dtype=np.float64), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    nbyte = 0
+    for asset in root.findall("asset"):
+      for el in asset.findall("texture"):
+        a = self._resolve("texture", el, None)
+        kind = {"2d": 0, "cube": 1, "skybox": 2}.get(a.get("type", "cube"))
+        if kind is None:
+          raise ValueError(f"texture {a.get('name', '')}: unknown type '{a.get('type')}'")
+        name = a.get("name") or os.path.splitext(os.path.basename(a.get("file", "")))[0]
+        tid = len(ttype)
+        self.tex_id[name] = tid
+        w, h = int(a.get("width", 0)), int(a.get("height", 0))
+        px = None
+        builtin = a.get("builtin", "none")
+        if kind == 0 and "file" in a:
+          path = os.path.join(self.basedir, self.texturedir, a["file"])
+          if not os.path.isfile(path):
+            self.tex_refused[tid] = f"texture {name}: file '{path}' not found"
+          elif path.lower().endswith(".png"):
+            h, w, spl, depth = _read_png(path)
+            spl = (spl >> 8) if depth == 16 else spl
+            px = (spl[:, :, :3] if spl.shape[2] >= 3 else np.repeat(spl[:, :, :1], 3, axis=2)).astype(np.uint8)
+            if a.get("hflip", "false") == "true":
+              px = px[:, ::-1]
+            if a.get("vflip", "false") == "true":
+              px = px[::-1]
+          else:
+            self.tex_refused[tid] = f"texture {name}: file type of '{a['file']}' is not supported (PNG only)"
+        elif kind == 0 and builtin != "none" and w > 0 and h > 0:
+          rgb1, rgb2 = byte(_floats(a.get("rgb1", "0.8 0.8 0.8"), 3)), byte(_floats(a.get("rgb2", "0.5 0.5 0.5"), 3))
+          px = np.empty((h, w, 3), dtype=np.uint8)
+          px[:] = rgb1
+          r, c = np.arange(h)[:, None], np.arange(w)[None, :]
+          if builtin == "checker":
+            px[(r < h // 2) != (c < w // 2)] = rgb2
+          elif builtin == "gradient":
+            t = (np.arange(h, dtype=np.float64) / max(h - 1, 1))[:, None, None]
+            f1, f2 = np.asarray(_floats(a.get("rgb1", "0.8 0.8 0.8"), 3)), np.asarray(_floats(a.get("rgb2", "0.5 0.5 0.5"), 3))
+            px[:] = byte(f1 + (f2 - f1) * t)
+          mark, markrgb = a.get("mark", "none"), byte(_floats(a.get("markrgb", "0 0 0"), 3))
+          if mark == "edge":
+            px[(r == 0) | (r == h - 1) | (c == 0) | (c == w - 1)] = markrgb
+          elif mark == "cross":
+            px[(r == h // 2) | (c == w // 2)] = markrgb
+        ttype.append(kind)
+        width.append(w)
+        height.append(h)
+        names.append(name)
+        if px is None:
+          adr.append(-1)
+        else:
+          adr.append(nbyte)
+          data.append(np.ascontiguousarray(px).reshape(-1))
+          nbyte += int(px.size)
+    m.ntex, m.ntexdata = len(ttype), nbyte
+    m.tex_type = np.array(ttype, dtype=np.int32)
+    m.tex_width, m.tex_height = np.array(width, dtype=np.int32), np.array(height, dtype=np.int32)
+    m.tex_nchannel = np.full(len(ttype), 3, dtype=np.int32)
+    m.tex_adr = np.array(adr, dtype=np.int64)
+    m.tex_data = np.concatenate(data) if data else np.zeros(0, dtype=np.uint8)
+    m.tex_names = names
+
   def _load_materials(self, root):
-    """<asset><material>: only the colour (mat_rgba, MuJoCo's default 1 1 1 1) is kept -- ray casting skips
-    geoms whose material is fully transparent."""
+    """<asset><material>: the colour (mat_rgba, MuJoCo's default 1 1 1 1; ray casting skips geoms whose material is
+    fully transparent) and the texture: mat_texid (nmat, 10) is -1 but for role 1 (mjTEXROLE_RGB), which holds the id
+    of the texture named by `texture` or by a child <layer role="rgb">; mat_texrepeat (default 1 1); mat_texuniform."""
     m = self.m
     self.mat_id = {}
-    rgba = []
+    rgba, texid, texrepeat, texuniform = [], [], [], []
     for asset in root.findall("asset"):
       for el in asset.findall("material"):
         a = self._resolve("material", el, None)
         self.mat_id[a.get("name", "")] = len(rgba)
         rgba.append(_floats(a.get("rgba", "1 1 1 1"), 4))
+        tex = a.get("texture")
+        for layer in el.findall("layer"):
+          if layer.get("role", "rgb") == "rgb":
+            tex = layer.get("texture", tex)
+        ids = [-1] * 10
+        if tex is not None:
+          if tex not in self.tex_id:
+            raise ValueError(f"material {a.get('name', '')}: unknown texture '{tex}'")
+          ids[1] = self.tex_id[tex]
+          if ids[1] in self.tex_refused:
+            raise NotImplementedError(self.tex_refused[ids[1]])
+        texid.append(ids)
+        texrepeat.append(_merge_vec([1.0, 1.0], _floats(a.get("texrepeat", "1 1"))))
+        texuniform.append(a.get("texuniform", "false") == "true")
     m.nmat = len(rgba)
     m.mat_rgba = np.array(rgba, dtype=np.float64).reshape(-1, 4)
+    m.mat_texid = np.array(texid, dtype=np.int32).reshape(-1, 10)
+    m.mat_texrepeat = np.array(texrepeat, dtype=np.float64).reshape(-1, 2)
+    m.mat_texuniform = np.array(texuniform, dtype=bool).reshape(-1)
 
   def _load_hfields(self, root):
     """<asset><hfield>: nrow x ncol elevation grid (row 0 at -y, MuJoCo's mjModel.hfield_data order), size =
@@ -2331,8 +2443,11 @@ def _bending_coef(x, mu, thickness):
   return (np.outer(c, c) * mu * thickness**3 / (8.0 * (a0 + a1))).reshape(-1)
 
 
-def _read_mesh_file(path):
-  """(vertices (n, 3) float64, triangles (t, 3) int64) of a binary / ASCII STL or an OBJ file."""
+def _read_mesh_file(path, texcoord=False):
+  """(vertices (n, 3) float64, triangles (t, 3) int64) of a binary / ASCII STL or an OBJ file.  texcoord: also the
+  texture coordinates (k, 2) of an OBJ's `vt` records, stored (u, 1 - v) as MuJoCo's OBJ loader does, and the
+  triangles' indices into them (t, 3); both None for an STL, an OBJ without faces and an OBJ in which any face corner
+  lacks a `vt`."""
   ext = os.path.splitext(path)[1].lower()
   with open(path, "rb") as fh:
     buf = fh.read()
@@ -2344,21 +2459,37 @@ def _read_mesh_file(path):
       n = int(np.frombuffer(buf, dtype="<u4", count=1, offset=80)[0])
       rec = np.dtype([("n", "<f4", 3), ("v", "<f4", 9), ("a", "<u2")])
       v = np.frombuffer(buf, dtype=rec, count=n, offset=84)["v"].reshape(-1, 3).astype(np.float64)
-    return v, np.arange(len(v)).reshape(-1, 3)
+    f = np.arange(len(v)).reshape(-1, 3)
+    return (v, f, None, None) if texcoord else (v, f)
   if ext == ".obj":
-    verts, faces = [], []
+    verts, faces, uvs, tfaces, all_vt = [], [], [], [], True
     for ln in buf.decode("utf-8", "replace").splitlines():
       p = ln.split()
       if not p:
         continue
       if p[0] == "v":
         verts.append([float(x) for x in p[1:4]])
+      elif p[0] == "vt":
+        uvs.append([float(p[1]), 1.0 - float(p[2]) if len(p) > 2 else 1.0])
       elif p[0] == "f":
-        idx = [int(t.split("/")[0]) for t in p[1:]]
+        corner = [t.split("/") for t in p[1:]]
+        idx = [int(c[0]) for c in corner]
         idx = [i - 1 if i > 0 else len(verts) + i for i in idx]
+        if all(len(c) > 1 and c[1] != "" for c in corner):
+          tdx = [int(c[1]) for c in corner]
+          tdx = [i - 1 if i > 0 else len(uvs) + i for i in tdx]
+        else:
+          all_vt, tdx = False, [0] * len(idx)
         for k in range(1, len(idx) - 1):  # fan triangulation
           faces.append([idx[0], idx[k], idx[k + 1]])
-    return np.array(verts, dtype=np.float64).reshape(-1, 3), np.array(faces, dtype=np.int64).reshape(-1, 3)
+          tfaces.append([tdx[0], tdx[k], tdx[k + 1]])
+    v, f = np.array(verts, dtype=np.float64).reshape(-1, 3), np.array(faces, dtype=np.int64).reshape(-1, 3)
+    if not texcoord:
+      return v, f
+    tf = np.array(tfaces, dtype=np.int64).reshape(-1, 3)
+    if not all_vt or not uvs or len(f) == 0 or tf.min() < 0 or tf.max() >= len(uvs):
+      return v, f, None, None
+    return v, f, np.array(uvs, dtype=np.float64).reshape(-1, 2), tf
   raise NotImplementedError(f"mesh file type '{ext}' is not supported (STL / OBJ only)")
 
 

@@ -1,7 +1,8 @@
 """Batched camera rendering: segmentation, depth and shaded RGB images of a model's cameras
 (mujoco_warp/_src/render.py `render`, io.py `create_render_context`, render_util.py readers).
 
-One HIP launch (`mjw_render_bvh`, or `mjw_render_flex` for a context made with `render_flex`; csrc/mjw_render.hip) on the Data's stream per `render` call: a workgroup per
+One HIP launch (`mjw_render_bvh`, `mjw_render_flex` for a context made with `render_flex`, `mjw_render_tex` for a context that has
+textures; csrc/mjw_render.hip) on the Data's stream per `render` call: a workgroup per
 world, camera and 16 x 16 pixel tile makes the pixel rays from `d.cam_xpos` / `d.cam_xmat` and the per-world
 camera parameters, finds the nearest geom with the geom loop `rays` uses, and writes every pixel of every
 enabled output.  No kinematics run here: the frames are those the last position stage left.
@@ -21,8 +22,15 @@ world, in one launch (`mjw_flex_refit`, csrc/mjw_flexrender.hip).  `render` does
 step and before `render`, as code written for the reference does.  The faces are never stored: the context keeps
 corner records and, per world, the node boxes and the vertex normals.
 
-There is no BVH over the geoms (they are culled by bounding ball and box per wave) or over heightfields, no textures
-and no orthographic cameras.
+Textures (`use_textures`, the default): the 2D textures the MJCF compiler kept are packed into the context, one word per
+texel, and the base colour of a pixel on a plane (uv = the hit in the plane's frame) or on a mesh with texture coordinates
+(uv = the barycentric mean of the hit face's) is multiplied by a bilinear, repeating sample of the texture its material names,
+before the ambient and light terms.  mat_texid / mat_texrepeat may be batched per world.  Other geom types, meshes without
+texture coordinates and flexes keep their colour; cube and skybox textures are never sampled.  A context without textures
+(use_textures=False, or a model with none) makes the launches it always made.
+
+There is no BVH over the geoms (they are culled by bounding ball and box per wave) or over heightfields and no
+orthographic cameras.
 """
 
 from __future__ import annotations
@@ -72,8 +80,14 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
   flexes the flag changes nothing.  Without it a model with flexes raises NotImplementedError: its flex elements
   would be silently invisible.
 
-  Accepted and ignored: `use_textures` (the MJCF compiler keeps no textures, colours are mat_rgba / geom_rgba) and
-  `use_precomputed_rays` (the rays are always made in the kernel, so per-world cam_fovy / cam_intrinsic work)."""
+  use_textures: every 2D texture of the model that has data is packed into rc.tex_data (int32, one r | g << 8 | b << 16 |
+  255 << 24 word per texel) with rc.tex_adr / tex_width / tex_height (ntex,; tex_adr -1 for a texture that is never
+  sampled), next to device copies of mesh_texcoord, mesh_texcoordadr and mesh_facetexcoord; rc.has_textures is then True
+  and `render` textures planes and meshes (module docstring).  With use_textures=False, and for a model without such
+  textures, these tables are empty and `render` is what it is without them, bit for bit.
+
+  Accepted and ignored: `use_precomputed_rays` (the rays are always made in the kernel, so per-world cam_fovy /
+  cam_intrinsic work)."""
   from .io import _device
 
   nflex = int(getattr(mjm, "nflex", 0))
@@ -145,7 +159,7 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
   else:
     node, tri, adr, bvh_depth = build_mesh_bvh(np.zeros((0, 3)), [], np.zeros((0, 3)), [], [])
   flex = {}
-  if nflex > 0:
+  if nflex > 0:  # (flexes take no texture: their colour stays flex_rgba)
     t = build_flex_tables(mjm, smooth=bool(flex_render_smooth))
     nnode, nfv = int(t["node"].shape[0]), int(mjm.nflexvert)
     rgba = np.asarray(getattr(mjm, "flex_rgba", np.tile([0.5, 0.5, 0.5, 1.0], (nflex, 1))), dtype=np.float32).reshape(nflex, 4)
@@ -164,8 +178,13 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
       _flex_counts=(nflex, nfv, int(mjm.nflexelem), int(mjm.nflexedge)),
       _flex_refit=False,
     )
+  tex = _texture_tables(mjm, bool(use_textures))
   return RenderContext(
     **flex,
+    has_textures=bool(tex["tex_data"].size),
+    tex_data=torch.as_tensor(tex["tex_data"], device=dev), tex_adr=i32(tex["tex_adr"]), tex_width=i32(tex["tex_width"]),
+    tex_height=i32(tex["tex_height"]), mesh_texcoord=torch.as_tensor(tex["mesh_texcoord"], device=dev),
+    mesh_texcoordadr=i32(tex["mesh_texcoordadr"]), mesh_facetexcoord=i32(tex["mesh_facetexcoord"]),
     nworld=nworld,
     nrender=ncam,
     cam_res=i32(res.reshape(ncam, 2)),
@@ -204,6 +223,66 @@ def create_render_context(mjm, nworld: int = 1, cam_res=None, render_rgb=None, r
     _nmesh=nmesh,
     _nmeshface=nmeshface,
   )
+
+
+def _texture_tables(mjm, use_textures: bool) -> dict:
+  """The host arrays of a context's texture tables: every 2D texture with data packed one word per texel, and the mesh
+  texcoord tables; all empty when use_textures is off or the model has no such texture."""
+  ntex = int(getattr(mjm, "ntex", 0))
+  out = dict(tex_data=np.zeros(0, np.int32), tex_adr=np.zeros(0, np.int32), tex_width=np.zeros(0, np.int32), tex_height=np.zeros(0, np.int32),
+             mesh_texcoord=np.zeros((0, 2), np.float32), mesh_texcoordadr=np.zeros(0, np.int32), mesh_facetexcoord=np.zeros((0, 3), np.int32))
+  if not use_textures or ntex == 0:
+    return out
+  adr, words, n = -np.ones(ntex, dtype=np.int64), [], 0
+  for i in range(ntex):
+    w, h, a = int(mjm.tex_width[i]), int(mjm.tex_height[i]), int(mjm.tex_adr[i])
+    if int(mjm.tex_type[i]) != 0 or a < 0 or w < 1 or h < 1:
+      continue
+    b = np.asarray(mjm.tex_data[a : a + 3 * w * h], dtype=np.uint32).reshape(w * h, 3)
+    words.append(b[:, 0] | b[:, 1] << 8 | b[:, 2] << 16 | np.uint32(255 << 24))
+    adr[i], n = n, n + w * h
+  if n == 0:
+    return out
+  if n >= 2**31:
+    raise ValueError("create_render_context: more than 2^31 texels")
+  nmesh, nface = int(getattr(mjm, "nmesh", 0)), int(getattr(mjm, "nmeshface", 0))
+  out.update(tex_data=np.concatenate(words).astype(np.uint32).view(np.int32), tex_adr=adr, tex_width=np.asarray(mjm.tex_width), tex_height=np.asarray(mjm.tex_height),
+             mesh_texcoord=np.ascontiguousarray(np.asarray(getattr(mjm, "mesh_texcoord", np.zeros((0, 2))), dtype=np.float32).reshape(-1, 2)),
+             mesh_texcoordadr=np.asarray(getattr(mjm, "mesh_texcoordadr", -np.ones(nmesh))).reshape(nmesh),
+             mesh_facetexcoord=np.asarray(getattr(mjm, "mesh_facetexcoord", np.zeros((nface, 3)))).reshape(nface, 3))
+  return out
+
+
+def _ctex(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CTexture:
+  """mjw_texture_t of a context that has textures and the Model's current mat_texid / mat_texrepeat (built per call: a
+  caller may have replaced them with per-world batches); ValueError when a table has not the shape its count asks for."""
+  dev = d.qpos.device
+  nmat = int(m.nmat)
+  c = _lib.CTexture()
+
+  def chk(owner, name, t, dtype, tail):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape[1:]) != tail:
+      raise ValueError(f"{who}: {owner}.{name} must be a contiguous {dtype} tensor of shape (n,{' ' + str(tail) if tail else ''}) on {dev}")
+    return t
+
+  for name, dtype, tail in (("tex_data", torch.int32, ()), ("tex_adr", torch.int32, ()), ("tex_width", torch.int32, ()), ("tex_height", torch.int32, ()),
+                            ("mesh_texcoord", torch.float32, (2,)), ("mesh_texcoordadr", torch.int32, ()), ("mesh_facetexcoord", torch.int32, (3,))):
+    setattr(c, name, chk("rc", name, getattr(rc, name), dtype, tail).data_ptr())
+  ntex = int(rc.tex_adr.shape[0])
+  if int(rc.tex_width.shape[0]) != ntex or int(rc.tex_height.shape[0]) != ntex:
+    raise ValueError(f"{who}: rc.tex_adr / tex_width / tex_height must hold the same number of textures")
+  nmesh, nface = int(rc.mesh_texcoordadr.shape[0]), int(rc.mesh_facetexcoord.shape[0])
+  if nmesh not in (0, int(m.nmesh)) or nface not in (0, int(m.nmeshface)):
+    raise ValueError(f"{who}: rc.mesh_texcoordadr / mesh_facetexcoord must hold {m.nmesh} meshes and {m.nmeshface} faces (or none)")
+  texid, texrep = getattr(m, "mat_texid", None), getattr(m, "mat_texrepeat", None)
+  texid, texrep = chk("m", "mat_texid", texid, torch.int32, (nmat, 10)), chk("m", "mat_texrepeat", texrep, torch.float32, (nmat, 2))
+  if texid.shape[0] < 1 or texrep.shape[0] < 1:
+    raise ValueError(f"{who}: m.mat_texid / m.mat_texrepeat need a leading batch dimension of at least 1")
+  c.ntex, c.ntexdata, c.nmat, c.nmesh, c.ntexcoord, c.nmeshface = ntex, int(rc.tex_data.shape[0]), nmat, nmesh, int(rc.mesh_texcoord.shape[0]), nface
+  c.mat_texid, c.mat_texid_nb = texid.data_ptr(), int(texid.shape[0])
+  c.mat_texrepeat, c.mat_texrepeat_nb = texrep.data_ptr(), int(texrep.shape[0])
+  c._keep = (texid, texrep)
+  return c
 
 
 def _crender(rc: RenderContext) -> _lib.CRender:
@@ -309,11 +388,12 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   (render.py:515-830), in one launch on the Data's stream; capturable in a graph.
 
   Segmentation: the geom id of the nearest drawn geom, -1 for background.  Depth: the distance along the
-  camera's optical axis, 0 for background.  RGB: mat_rgba (geoms with a material) or geom_rgba, shaded with a
+  camera's optical axis, 0 for background.  RGB: mat_rgba (geoms with a material) or geom_rgba, on a context that has
+  textures times the texture sample of planes and of meshes with texture coordinates (module docstring), shaded with a
   hemispheric ambient term and the active lights (directional, point with 1 / (1 + 0.02 r^2), spot with the
   reference's cone), clamped and packed as a << 24 | r << 16 | g << 8 | b; background (25, 25, 51, 255).  A geom
-  is drawn iff its group is enabled in the context: alpha plays no part.  cam_fovy, cam_intrinsic, geom_rgba
-  and mat_rgba may be batched per world.  The camera, light and geom frames are those of the last position
+  is drawn iff its group is enabled in the context: alpha plays no part.  cam_fovy, cam_intrinsic, geom_rgba,
+  mat_rgba, mat_texid and mat_texrepeat may be batched per world.  The camera, light and geom frames are those of the last position
   stage (`forward`, `step`, `kinematics` + `camlight`).  Meshes are walked through the context's BVHs; with a
   per-world batched `m.mesh_vert` (leading dim > 1), which the trees were not built from, the launch loops over
   every face instead.  Both give the same images bit for bit.
@@ -339,10 +419,20 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   bvh = _cbvh(rc, m, d, "render")
   rm = _ray_model(m)
   c = _crender(rc)
+  fr = None
   if _is_flex(rc):
     fr = _cflex(rc, m, d, "render")
     if not rc._flex_refit:
       raise ValueError("render: the context's flex trees have never been refit: call refit_bvh(m, d, rc) after the step and before render")
+  if bool(getattr(rc, "has_textures", False)):
+    tex = _ctex(rc, m, d, "render")
+    if c.ntile == 0:
+      return
+    rcode = _lib.lib().mjw_render_tex(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), ctypes.byref(fr) if fr is not None else None,
+                                      ctypes.byref(tex), _stream(d))
+    _lib.check(rcode, "mjw_render_tex")
+    return
+  if fr is not None:
     if c.ntile == 0:
       return
     rcode = _lib.lib().mjw_render_flex(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), ctypes.byref(fr), _stream(d))

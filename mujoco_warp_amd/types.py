@@ -409,7 +409,14 @@ class RenderContext(_Container):
   (nmesh, 4) int32, empty for a model without meshes; bvh_leaf_size and bvh_max_depth are host ints.  `render` and
   `rays(rc=...)` walk them for the meshes of at least bvh_min_faces faces (a host int, default bvh.BVH_MIN_FACES; set
   it to 0 to walk every mesh) and loop over the faces of the smaller ones, with the same results either way.
-  There is no BVH over the geoms and no texture.
+  There is no BVH over the geoms.
+
+  Textures (use_textures; `render` multiplies the base colour of planes and of meshes with texcoords by a bilinear
+  sample of the material's 2D texture): tex_data (texels,) int32, one r | g << 8 | b << 16 | 255 << 24 word per texel
+  of every 2D texture that has data, rows in the texture's order; tex_adr / tex_width / tex_height (ntex,) int32, the
+  first word of each texture (-1: never sampled) and its size; mesh_texcoord (ntexcoord, 2) float32, mesh_texcoordadr
+  (nmesh,) int32 (-1: the mesh has none) and mesh_facetexcoord (nmeshface, 3) int32 (indices local to the mesh).  All
+  are empty with use_textures=False and for a model without such textures; has_textures says which.
 
   A context made with render_flex=True also holds the flex tables (bvh.py `build_flex_tables`: flex_info, flex_corner,
   flex_elem_vert, flex_edge_vert, flex_inc_adr, flex_inc, flex_bvh_node, flex_bvh_tri, flex_bvh_level, flex_radius,
