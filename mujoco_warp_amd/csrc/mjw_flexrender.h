@@ -27,7 +27,7 @@ struct FlexArgs {
 // host: 1 when there are flexes to refit / draw, 0 when there are none, < 0 refused
 inline int check_flex_args(const char* who, const mjw_model_t* m, const mjw_data_t* d, const mjw_flexrender_t* fr, FlexArgs& fx) {
   const std::string w(who);
-  if (!fr) return set_last_error(-1, (w + ": null flex render tables").c_str());
+  if (!fr) return refuse_null(who, "flex render tables");
   if (fr->nflex != m->nflex || fr->nflexvert != m->nflexvert || fr->nflexelem != m->nflexelem || fr->nflexedge != m->nflexedge)
     return set_last_error(-4, (w + ": the flex tables were built for another model (nflex / nflexvert / nflexelem / nflexedge)").c_str());
   if (fr->nface < 0 || fr->nnode < 0 || fr->ninc < 0 || fr->nlevel < 0 || fr->leaf_size > BVH_LEAF || fr->max_depth > 32)

@@ -13,6 +13,8 @@
 // unchanged; these live in their own namespace.
 #pragma once
 
+#include <type_traits>
+
 #include "mjw_common.h"
 
 namespace mjw {
@@ -389,8 +391,8 @@ inline void fill_geom_args(GeomArgs& a, const mjw_model_t* m, const mjw_data_t* 
   a.hfield_nrow = m->hfield_nrow; a.hfield_ncol = m->hfield_ncol; a.hfield_adr = m->hfield_adr;
 }
 
-// the mesh BVHs of a render context (mjw_bvh_t; bvh.py has the layout).  A block of its own, handed only to the
-// kernels built with BVH = true, so that GeomArgs and the kernels without a BVH stay as they are.
+// the mesh BVHs of a render context (mjw_bvh_t; bvh.py has the layout).  A block of its own, read only by
+// the kernels built with BVH = true (the others get it zeroed and never load it), so that GeomArgs stays as it is.
 struct BvhArgs {
   int nnode, ntri, nmesh, min_faces;  // min_faces: meshes with fewer faces keep the face loop
   const float* node;  // (nnode, 8): box min 3, box max 3, two ints
@@ -401,10 +403,13 @@ constexpr int BVH_LEAF = 4;     // triangles per leaf at the most (bvh.py BVH_LE
 constexpr int BVH_STACK = 64;   // traversal stack entries: one per lane of a VGPR; the trees have at most 32 levels
 constexpr int BVH_AXIS_SHIFT = 29;
 
-// host: whether a call with this bvh walks the trees (1), runs the face loop (0), or is refused (< 0)
+// host: the one refusal of a null table that the entry `who` requires ("<who>: null <what>", -1)
+inline int refuse_null(const char* who, const char* what) { return set_last_error(-1, (std::string(who) + ": null " + what).c_str()); }
+
+// host: whether a call with this bvh (not null: the entries refuse that) walks the trees (1), runs the face loop (0),
+// or is refused (< 0)
 inline int check_bvh_args(const char* who, const mjw_model_t* m, const mjw_ray_model_t* rm, const mjw_bvh_t* bvh, BvhArgs& bv) {
   const std::string w(who);
-  if (!bvh) return set_last_error(-1, (w + ": null bvh").c_str());
   if (bvh->nmesh != m->nmesh || bvh->ntri != rm->nmeshface) return set_last_error(-4, (w + ": the bvh was built for another model (nmesh / nmeshface)").c_str());
   if (bvh->nnode < 0 || bvh->leaf_size > BVH_LEAF || bvh->max_depth > 32) return set_last_error(-4, (w + ": bvh nnode / leaf_size / max_depth out of range").c_str());
   if (rm->nmeshface <= 0 || m->nmesh <= 0 || bvh->nnode == 0 || m->mesh_vert_nb > 1) return 0;
@@ -412,6 +417,17 @@ inline int check_bvh_args(const char* who, const mjw_model_t* m, const mjw_ray_m
   bv.nnode = bvh->nnode; bv.ntri = bvh->ntri; bv.nmesh = bvh->nmesh; bv.min_faces = bvh->min_faces;
   bv.node = bvh->node; bv.tri = bvh->tri; bv.adr = bvh->adr;
   return 1;
+}
+
+// host: a runtime flag as a compile-time constant.  f is a generic lambda and receives std::true_type or std::false_type;
+// nested once per flag, the innermost body names one instantiation by the flags themselves, so that the launchers hold
+// one launch each and no table of instantiations that could be indexed wrongly.
+template <class F>
+inline void with_flag(bool on, F&& f) {
+  if (on)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
 }
 
 __device__ __forceinline__ const float* row(const float* p, int nb, long cnt, int w) { return nb <= 1 ? p : p + (long)(w % nb) * cnt; }
@@ -608,7 +624,7 @@ __device__ __forceinline__ float bvh_walk(const Src& src, const float* nodes, in
 template <bool ANYHIT>
 __device__ __forceinline__ float mesh_bvh(const BvhArgs& bv, int mesh, const float* vert, const int* face, int nface, bool cand,
                                           const float* lp, const float* lv, const float* b0, const float* b1, float best, float* nl,
-                                          int* face_out = nullptr) {
+                                          int* face_out) {
   if (face_out) *face_out = -1;
   if (mesh >= bv.nmesh) return -1.0f;  // (uniform, like every test of the tables below: a table that does not fit hits nothing)
   const int* adr = bv.adr + 4 * (long)mesh;
@@ -653,7 +669,7 @@ __device__ __forceinline__ void trace_chunk(const GeomArgs& a, const BvhArgs& bv
       const int f0 = a.mesh_faceadr[mesh], f1 = min(f0 + a.mesh_facenum[mesh], a.nmeshface);
       if (BVH && f1 - f0 >= bv.min_faces) {  // (uniform)
         if (f0 < 0 || f1 < f0) continue;
-        x = mesh_bvh<ANYHIT>(bv, mesh, vert, a.mesh_face + 3 * (long)f0, f1 - f0, cand, lp, lv, b0, b1, best, nl);
+        x = mesh_bvh<ANYHIT>(bv, mesh, vert, a.mesh_face + 3 * (long)f0, f1 - f0, cand, lp, lv, b0, b1, best, nl, nullptr);
       } else {
         for (int f = f0; f < f1; f++) {
           const int* idx = a.mesh_face + 3 * (long)f;

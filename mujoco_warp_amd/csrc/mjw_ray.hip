@@ -9,8 +9,9 @@
 // worked out once per workgroup while staging, the inner loop tests only the flag and the ray's bodyexclude.
 // A geom no lane's bounding test passes is skipped by the whole wave (ballot), so the mesh and heightfield
 // loops run only in waves with a candidate ray.  The loop itself (staging, culling, nearest hit) is geom_loop
-// of mjw_ray.h, which the render kernel (mjw_render.hip) calls too.  mjw_rays_bvh launches the same body built with
-// BVH = true (rays_bvh_kernel): meshes are walked through the static trees of a render context (mesh_bvh, mjw_ray.h).
+// of mjw_ray.h, which the render kernel (mjw_render.hip) calls too.  There is one kernel, rays_kernel<NT, BVH>;
+// mjw_rays_bvh launches it with BVH = true: meshes are walked through the static trees of a render context (mesh_bvh,
+// mjw_ray.h).  mjw_rays, and a context whose trees do not serve the call, launch BVH = false: every face of every mesh.
 #include "mjw_common.h"
 #include "mjw_ray.h"
 
@@ -53,17 +54,11 @@ __device__ __forceinline__ void rays_body(const RayArgs& a, const BvhArgs& bv, f
   }
 }
 
-template <int NT>
-__global__ void __launch_bounds__(NT) rays_kernel(const RayArgs a) {
+// BVH: the meshes are walked through the BVHs of a render context (bv); without it bv is never read
+template <int NT, bool BVH>
+__global__ void __launch_bounds__(NT) rays_kernel(const RayArgs a, const BvhArgs bv) {
   __shared__ float recs[RAY_CHUNK * RECW];
-  rays_body<NT, false>(a, BvhArgs{}, recs);
-}
-
-// the same with the meshes walked through the BVHs of a render context
-template <int NT>
-__global__ void __launch_bounds__(NT) rays_bvh_kernel(const RayArgs a, const BvhArgs bv) {
-  __shared__ float recs[RAY_CHUNK * RECW];
-  rays_body<NT, true>(a, bv, recs);
+  rays_body<NT, BVH>(a, bv, recs);
 }
 
 }  // namespace ray
@@ -71,7 +66,7 @@ __global__ void __launch_bounds__(NT) rays_bvh_kernel(const RayArgs a, const Bvh
 
 static int rays_launch(const char* who, const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb,
                        const float* vec, int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude, float* dist,
-                       int* geomid, float* normal, const mjw_bvh_t* bvh, bool with_bvh, void* stream) {
+                       int* geomid, float* normal, const mjw_bvh_t* bvh, void* stream) {
   using namespace mjw::ray;
   const std::string w(who);
   if (!m || !d || !rm) return mjw::set_last_error(-1, (w + ": null model / data / ray model").c_str());
@@ -79,7 +74,7 @@ static int rays_launch(const char* who, const mjw_model_t* m, const mjw_data_t* 
   BvhArgs bv;
   memset(&bv, 0, sizeof(bv));
   int walk = 0;
-  if (with_bvh && (walk = check_bvh_args(who, m, rm, bvh, bv)) < 0) return walk;
+  if (bvh && (walk = check_bvh_args(who, m, rm, bvh, bv)) < 0) return walk;
   if (nray == 0 || d->nworld <= 0) return 0;
   if (!pnt || !vec || !bodyexclude || !dist || !geomid || !normal) return mjw::set_last_error(-1, (w + ": null ray / output array").c_str());
   if ((pnt_nb != 1 && pnt_nb != d->nworld) || (vec_nb != 1 && vec_nb != d->nworld))
@@ -108,16 +103,12 @@ static int rays_launch(const char* who, const mjw_model_t* m, const mjw_data_t* 
   a.ntile = (nray + nt - 1) / nt;
   const long nblock = (long)a.nworld * a.ntile;
   if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, (w + ": nworld x ray tiles exceeds the grid limit").c_str());
-  if (walk) {
-    if (nt == 64)
-      hipLaunchKernelGGL(rays_bvh_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a, bv);
-    else
-      hipLaunchKernelGGL(rays_bvh_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a, bv);
-  } else if (nt == 64) {
-    hipLaunchKernelGGL(rays_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(rays_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a);
-  }
+  with_flag(nt == 64, [&](auto small) {
+    with_flag(walk != 0, [&](auto bvh_on) {
+      constexpr int NT = decltype(small)::value ? 64 : 256;
+      hipLaunchKernelGGL((rays_kernel<NT, decltype(bvh_on)::value>), dim3((unsigned)nblock), dim3(NT), 0, s, a, bv);
+    });
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mjw::set_last_error((int)e, hipGetErrorString(e));
   return 0;
@@ -127,12 +118,14 @@ extern "C" int mjw_rays(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray
                         const float* vec, int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude,
                         float* dist, int* geomid, float* normal, void* stream) {
   return rays_launch("mjw_rays", m, d, rm, pnt, pnt_nb, vec, vec_nb, nray, geomgroup, flg_static, bodyexclude, dist, geomid, normal, nullptr,
-                     false, stream);
+                     stream);
 }
 
 extern "C" int mjw_rays_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const float* pnt, int pnt_nb,
                             const float* vec, int vec_nb, int nray, const int* geomgroup, int flg_static, const int* bodyexclude,
                             float* dist, int* geomid, float* normal, const mjw_bvh_t* bvh, void* stream) {
+  // (a null bvh is refused where it always was: after the model pointers and nray)
+  if (m && d && rm && nray >= 0 && !bvh) return mjw::ray::refuse_null("mjw_rays_bvh", "bvh");
   return rays_launch("mjw_rays_bvh", m, d, rm, pnt, pnt_nb, vec, vec_nb, nray, geomgroup, flg_static, bodyexclude, dist, geomid, normal, bvh,
-                     true, stream);
+                     stream);
 }

@@ -15,6 +15,9 @@
 //
 // Flexes (mjw_render_flex; FLEX = true): after the geom loop every ray goes through flex_loop (mjw_flexrender.h), for
 // the first hit and for each shadow ray; a flex pixel has segmentation -2, the colour flex_rgba and no material.
+//
+// One kernel, render_kernel<NT, BVH, FLEX, TEX>, serves the four entries (mjw_render, _bvh, _flex, _tex): render_launch
+// turns "the context has trees that serve this call / flexes / textures" into the three flags, NT is 64 or 256.
 #include "mjw_common.h"
 #include "mjw_ray.h"
 #include "mjw_flexrender.h"
@@ -115,7 +118,8 @@ __device__ __forceinline__ void tex_sample(const int* data, int W, int H, const 
 // Multiplies base by the texel colour of the lane's first hit (geom bid at distance best along pnt + x vec) where the
 // rules above give it one.  Every lane of the wave must call it: the face of a mesh hit is found again here, one hit
 // mesh geom of the wave at a time, by the walk or the face loop that found it in trace_chunk (the nearest triangle,
-// the lowest face id among equal distances), so the kernels without textures carry no face id.
+// the lowest face id among equal distances), so the kernels without textures carry no face id.  The block is a second
+// copy of trace_chunk's on purpose: one shared routine gave the same bits but slower textured launches.
 // recs: the staged records of the model's only chunk (ngeom <= RAY_CHUNK: the primary rays left them in LDS), else null.
 template <bool BVH>
 __device__ __forceinline__ void tex_shade(const GeomArgs& g, const BvhArgs& bv, const TexArgs& tx, int wid, const float* recs, bool on, int bid,
@@ -217,8 +221,8 @@ __device__ __forceinline__ void tex_shade(const GeomArgs& g, const BvhArgs& bv, 
   }
 }
 
-template <int NT, bool BVH, bool FLEX, bool TEX = false>
-__device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& bv, const FlexArgs& fx, float* recs, const TexArgs* tx = nullptr) {
+template <int NT, bool BVH, bool FLEX, bool TEX>
+__device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& bv, const FlexArgs& fx, const TexArgs& tx, float* recs) {
   const int tid = threadIdx.x;
   const int wid = blockIdx.x / a.ntile, t = blockIdx.x - wid * a.ntile;
   const int ci = a.tile[4 * t], x0 = a.tile[4 * t + 1], y0 = a.tile[4 * t + 2];
@@ -274,7 +278,7 @@ __device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& 
   } else if (bid >= 0) {
     for (int i = 0; i < 3; i++) base[i] = col[i];
   }
-  if (TEX) tex_shade<BVH>(a.g, bv, *tx, wid, a.g.ngeom <= RAY_CHUNK ? recs : nullptr, active && bid >= 0 && fid < 0, bid, matid, pnt, vec, best, base);
+  if (TEX) tex_shade<BVH>(a.g, bv, tx, wid, a.g.ngeom <= RAY_CHUNK ? recs : nullptr, active && bid >= 0 && fid < 0, bid, matid, pnt, vec, best, base);
   const float hp[3] = {pnt[0] + vec[0] * best, pnt[1] + vec[1] * best, pnt[2] + vec[2] * best};
   float n[3] = {bn[0], bn[1], bn[2]};
   if (!(dot3(n, n) > 0.0f)) { n[0] = 0.0f; n[1] = 0.0f; n[2] = 1.0f; }
@@ -334,36 +338,17 @@ __device__ __forceinline__ void render_body(const RenderArgs& a, const BvhArgs& 
   }
 }
 
-template <int NT>
-__global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a) {
+// The one render kernel.  BVH: the meshes are walked through the BVHs of the render context (bv), else face by face;
+// FLEX: the flexes of the context (fx) are drawn too; TEX: planes and meshes take their textures (tx).  Every
+// instantiation takes all four blocks: one whose flag is off is zeroed by the host and never loaded, and costs no register.
+template <int NT, bool BVH, bool FLEX, bool TEX>
+__global__ void __launch_bounds__(NT) render_kernel(const RenderArgs a, const BvhArgs bv, const FlexArgs fx, const TexArgs tx) {
   __shared__ float recs[RAY_CHUNK * RECW];
-  render_body<NT, false, false>(a, BvhArgs{}, FlexArgs{}, recs);
-}
-
-// the same with the meshes walked through the BVHs of the render context
-template <int NT>
-__global__ void __launch_bounds__(NT) render_bvh_kernel(const RenderArgs a, const BvhArgs bv) {
-  __shared__ float recs[RAY_CHUNK * RECW];
-  render_body<NT, true, false>(a, bv, FlexArgs{}, recs);
-}
-
-// the same with the flexes of the render context drawn too, the meshes through their BVHs or face by face
-template <int NT, bool BVH>
-__global__ void __launch_bounds__(NT) render_flex_kernel(const RenderArgs a, const BvhArgs bv, const FlexArgs fx) {
-  __shared__ float recs[RAY_CHUNK * RECW];
-  render_body<NT, BVH, true>(a, bv, fx, recs);
-}
-
-// the same with textures (TexArgs), with or without the BVHs and the flexes
-template <int NT, bool BVH, bool FLEX>
-__global__ void __launch_bounds__(NT) render_tex_kernel(const RenderArgs a, const BvhArgs bv, const FlexArgs fx, const TexArgs tx) {
-  __shared__ float recs[RAY_CHUNK * RECW];
-  render_body<NT, BVH, FLEX, true>(a, bv, fx, recs, &tx);
+  render_body<NT, BVH, FLEX, TEX>(a, bv, fx, tx, recs);
 }
 
 // host: the checks of mjw_texture_t; 1: sample, 0: nothing to sample (the call is the one without textures), < 0: refused
 static int check_tex_args(const mjw_model_t* m, const mjw_ray_model_t* rm, const mjw_texture_t* t, TexArgs& tx) {
-  if (!t) return set_last_error(-1, "mjw_render_tex: null texture tables");
   if (t->ntex < 0 || t->ntexdata < 0 || t->nmat < 0 || t->nmesh < 0 || t->ntexcoord < 0 || t->nmeshface < 0)
     return set_last_error(-4, "mjw_render_tex: negative count");
   if (t->mat_texid_nb < 1 || t->mat_texrepeat_nb < 1) return set_last_error(-4, "mjw_render_tex: mat_texid / mat_texrepeat batch size < 1");
@@ -387,29 +372,24 @@ static int check_tex_args(const mjw_model_t* m, const mjw_ray_model_t* rm, const
 }  // namespace ray
 }  // namespace mjw
 
-template <int NT, bool BVH, bool FLEX>
-static void launch_tex(long nblock, hipStream_t s, const mjw::ray::RenderArgs& a, const mjw::ray::BvhArgs& bv, const mjw::ray::FlexArgs& fx,
-                       const mjw::ray::TexArgs& tx) {
-  hipLaunchKernelGGL((mjw::ray::render_tex_kernel<NT, BVH, FLEX>), dim3((unsigned)nblock), dim3(NT), 0, s, a, bv, fx, tx);
-}
-
-static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
-                         bool with_bvh, const mjw_flexrender_t* fr, bool with_flex, void* stream, const mjw_texture_t* tex = nullptr,
-                         bool with_tex = false) {
+// The launch every entry below ends in; who: the entry's name for the messages about its own tables.  A null bvh, fr or
+// tex means "absent": no walk, no flexes, no textures.  The entries refuse a null table their contract requires.
+static int render_launch(const char* who, const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc,
+                         const mjw_bvh_t* bvh, const mjw_flexrender_t* fr, const mjw_texture_t* tex, void* stream) {
   using namespace mjw::ray;
   if (!m || !d || !rm || !rc) return mjw::set_last_error(-1, "mjw_render: null model / data / ray model / render context");
   TexArgs tx;
   memset(&tx, 0, sizeof(tx));
   int textured = 0;
-  if (with_tex && (textured = check_tex_args(m, rm, tex, tx)) < 0) return textured;
+  if (tex && (textured = check_tex_args(m, rm, tex, tx)) < 0) return textured;
   BvhArgs bv;
   memset(&bv, 0, sizeof(bv));
   int walk = 0;
-  if (with_bvh && (walk = check_bvh_args(with_flex ? "mjw_render_flex" : "mjw_render_bvh", m, rm, bvh, bv)) < 0) return walk;
+  if (bvh && (walk = check_bvh_args(who, m, rm, bvh, bv)) < 0) return walk;
   FlexArgs fx;
   memset(&fx, 0, sizeof(fx));
   int flex = 0;
-  if (with_flex && (flex = check_flex_args("mjw_render_flex", m, d, fr, fx)) < 0) return flex;
+  if (fr && (flex = check_flex_args(who, m, d, fr, fx)) < 0) return flex;
   if (rc->ntile < 0 || rc->nrender < 0) return mjw::set_last_error(-4, "mjw_render: ntile / nrender < 0");
   if (rc->ntile == 0 || d->nworld <= 0) return 0;
   if (rc->tile_threads != 64 && rc->tile_threads != 256) return mjw::set_last_error(-4, "mjw_render: tile_threads must be 64 or 256");
@@ -444,56 +424,44 @@ static int render_launch(const mjw_model_t* m, const mjw_data_t* d, const mjw_ra
   hipStream_t s = (hipStream_t)stream;
   const long nblock = (long)a.nworld * a.ntile;
   if (nblock > 0x7fffffffL) return mjw::set_last_error(-2, "mjw_render: nworld x tiles exceeds the grid limit");
-  if (textured) {
-    const int k = (rc->tile_threads == 64 ? 4 : 0) | (walk ? 2 : 0) | (flex ? 1 : 0);
-    switch (k) {
-      case 0: launch_tex<256, false, false>(nblock, s, a, bv, fx, tx); break;
-      case 1: launch_tex<256, false, true>(nblock, s, a, bv, fx, tx); break;
-      case 2: launch_tex<256, true, false>(nblock, s, a, bv, fx, tx); break;
-      case 3: launch_tex<256, true, true>(nblock, s, a, bv, fx, tx); break;
-      case 4: launch_tex<64, false, false>(nblock, s, a, bv, fx, tx); break;
-      case 5: launch_tex<64, false, true>(nblock, s, a, bv, fx, tx); break;
-      case 6: launch_tex<64, true, false>(nblock, s, a, bv, fx, tx); break;
-      default: launch_tex<64, true, true>(nblock, s, a, bv, fx, tx); break;
-    }
-  } else if (flex) {
-    const bool small = rc->tile_threads == 64;
-    if (walk && small) hipLaunchKernelGGL((render_flex_kernel<64, true>), dim3((unsigned)nblock), dim3(64), 0, s, a, bv, fx);
-    else if (walk) hipLaunchKernelGGL((render_flex_kernel<256, true>), dim3((unsigned)nblock), dim3(256), 0, s, a, bv, fx);
-    else if (small) hipLaunchKernelGGL((render_flex_kernel<64, false>), dim3((unsigned)nblock), dim3(64), 0, s, a, bv, fx);
-    else hipLaunchKernelGGL((render_flex_kernel<256, false>), dim3((unsigned)nblock), dim3(256), 0, s, a, bv, fx);
-  } else if (walk) {
-    if (rc->tile_threads == 64)
-      hipLaunchKernelGGL(render_bvh_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a, bv);
-    else
-      hipLaunchKernelGGL(render_bvh_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a, bv);
-  } else if (rc->tile_threads == 64) {
-    hipLaunchKernelGGL(render_kernel<64>, dim3((unsigned)nblock), dim3(64), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(render_kernel<256>, dim3((unsigned)nblock), dim3(256), 0, s, a);
-  }
+  with_flag(rc->tile_threads == 64, [&](auto small) {
+    with_flag(walk != 0, [&](auto bvh_on) {
+      with_flag(flex != 0, [&](auto flex_on) {
+        with_flag(textured != 0, [&](auto tex_on) {
+          constexpr int NT = decltype(small)::value ? 64 : 256;
+          hipLaunchKernelGGL((render_kernel<NT, decltype(bvh_on)::value, decltype(flex_on)::value, decltype(tex_on)::value>),
+                             dim3((unsigned)nblock), dim3(NT), 0, s, a, bv, fx, tx);
+        });
+      });
+    });
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mjw::set_last_error((int)e, hipGetErrorString(e));
   return 0;
 }
 
+// The entries.  A null table that an entry requires is refused where it always was, after the model pointers, which are
+// the launcher's to refuse; mjw_render_flex's null fr now comes before the launcher looks into the bvh.
 extern "C" int mjw_render(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, void* stream) {
-  return render_launch(m, d, rm, rc, nullptr, false, nullptr, false, stream);
+  return render_launch("mjw_render", m, d, rm, rc, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int mjw_render_bvh(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc,
                               const mjw_bvh_t* bvh, void* stream) {
-  return render_launch(m, d, rm, rc, bvh, true, nullptr, false, stream);
+  if (m && d && rm && rc && !bvh) return mjw::ray::refuse_null("mjw_render_bvh", "bvh");
+  return render_launch("mjw_render_bvh", m, d, rm, rc, bvh, nullptr, nullptr, stream);
 }
 
 extern "C" int mjw_render_flex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc,
                                const mjw_bvh_t* bvh, const mjw_flexrender_t* fr, void* stream) {
-  return render_launch(m, d, rm, rc, bvh, bvh != nullptr, fr, true, stream);
+  if (m && d && rm && rc && !fr) return mjw::ray::refuse_null("mjw_render_flex", "flex render tables");
+  return render_launch("mjw_render_flex", m, d, rm, rc, bvh, fr, nullptr, stream);
 }
 
 extern "C" int mjw_sizeof_texture(void) { return (int)sizeof(mjw_texture_t); }
 
 extern "C" int mjw_render_tex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
                               const mjw_flexrender_t* fr, const mjw_texture_t* tex, void* stream) {
-  return render_launch(m, d, rm, rc, bvh, bvh != nullptr, fr, fr != nullptr, stream, tex, true);
+  if (m && d && rm && rc && !tex) return mjw::ray::refuse_null("mjw_render_tex", "texture tables");
+  return render_launch("mjw_render_tex", m, d, rm, rc, bvh, fr, tex, stream);
 }

@@ -25,43 +25,21 @@ def _ray_model(m: Model) -> _lib.CRayModel:
   """The side struct mjw_ray_model_t from the Model's current tensors (built per call: a caller may have
   replaced geom_rgba / mat_rgba with per-world batches)."""
   ng, nmat, nface = int(m.ngeom), int(m.nmat), int(m.nmeshface)
-
-  def chk(name, dtype, numel=None, per_batch=None):
-    t = getattr(m, name)
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != m.geom_type.device:
-      raise ValueError(f"model field {name}: a contiguous {dtype} tensor on {m.geom_type.device}")
-    if numel is not None and t.numel() != numel:
-      raise ValueError(f"model field {name}: expected {numel} values, got shape {tuple(t.shape)}")
-    if per_batch is not None and (t.dim() < 1 or t.shape[0] < 1 or t.numel() != t.shape[0] * per_batch):
-      raise ValueError(f"model field {name}: expected (nb, {per_batch}) values, got shape {tuple(t.shape)}")
-    return t
-
+  chk = lambda name, dtype, *shape: _lib.check_tensor("ray model", "m." + name, getattr(m, name), dtype, m.geom_type.device, shape)
   c = _lib.CRayModel()
   c.ngeom, c.nmat, c.nmeshface = ng, nmat, nface
   c.geom_group = chk("geom_group", torch.int32, ng).data_ptr()
   c.geom_matid = chk("geom_matid", torch.int32, ng).data_ptr()
-  rgba = chk("geom_rgba", torch.float32, per_batch=ng * 4)
+  rgba, mat = chk("geom_rgba", torch.float32, None, ng, 4), chk("mat_rgba", torch.float32, None, nmat, 4)
+  if rgba.shape[0] < 1 or mat.shape[0] < 1:
+    raise ValueError("ray model: m.geom_rgba / m.mat_rgba need a leading batch dimension of at least 1")
   c.geom_rgba, c.geom_rgba_nb = rgba.data_ptr(), int(rgba.shape[0])
-  mat = chk("mat_rgba", torch.float32, per_batch=nmat * 4)
   c.mat_rgba, c.mat_rgba_nb = mat.data_ptr(), int(mat.shape[0])
-  c.mesh_face = chk("mesh_face", torch.int32, nface * 3).data_ptr()
-  c.mesh_faceadr = chk("mesh_faceadr", torch.int32).data_ptr()
-  c.mesh_facenum = chk("mesh_facenum", torch.int32).data_ptr()
+  c.mesh_face = chk("mesh_face", torch.int32, nface, 3).data_ptr()
+  c.mesh_faceadr = chk("mesh_faceadr", torch.int32, None).data_ptr()
+  c.mesh_facenum = chk("mesh_facenum", torch.int32, None).data_ptr()
   c._keep = (rgba, mat)  # the tensors whose pointers the struct holds
   return c
-
-
-def _check(name, t, dtype, shape, device):
-  if not isinstance(t, torch.Tensor):
-    raise ValueError(f"rays: {name} must be a torch tensor")
-  if t.dtype != dtype:
-    raise ValueError(f"rays: {name} must be {dtype}, got {t.dtype}")
-  if tuple(t.shape) != tuple(shape):
-    raise ValueError(f"rays: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-  if t.device != device:
-    raise ValueError(f"rays: {name} is on {t.device}, the Data is on {device}")
-  if not t.is_contiguous():
-    raise ValueError(f"rays: {name} must be contiguous")
 
 
 def rays(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Optional[Sequence[int]], flg_static: bool,
@@ -82,24 +60,21 @@ def rays(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Opt
 
     if not isinstance(rc, RenderContext):
       raise NotImplementedError("rays: rc must be None or a RenderContext from create_render_context (its mesh BVHs are walked)")
-    from .render import _cbvh
+    from .render import _cbvh, _made_for
 
+    _made_for("rays", rc, m, d)
     bvh = _cbvh(rc, m, d, "rays")
   dev = d.qpos.device
   nworld = int(d.nworld)
-  if not isinstance(pnt, torch.Tensor) or pnt.dim() != 3 or pnt.shape[2] != 3:
-    raise ValueError("rays: pnt must be a float32 tensor of shape (nb, nray, 3)")
-  nb, nray = int(pnt.shape[0]), int(pnt.shape[1])
-  if nb != 1 and nb != nworld:
-    raise ValueError(f"rays: pnt / vec batch must be 1 or nworld = {nworld}, got {nb}")
-  _check("pnt", pnt, torch.float32, (nb, nray, 3), dev)
-  if not isinstance(vec, torch.Tensor) or vec.dim() != 3 or (int(vec.shape[0]) != 1 and int(vec.shape[0]) != nworld):
-    raise ValueError(f"rays: vec must have shape (nb, {nray}, 3) with nb = 1 or nworld = {nworld}")
-  _check("vec", vec, torch.float32, (int(vec.shape[0]), nray, 3), dev)
-  _check("bodyexclude", bodyexclude, torch.int32, (nray,), dev)
-  _check("dist", dist, torch.float32, (nworld, nray), dev)
-  _check("geomid", geomid, torch.int32, (nworld, nray), dev)
-  _check("normal", normal, torch.float32, (nworld, nray, 3), dev)
+  chk = lambda name, t, dtype, *shape: _lib.check_tensor("rays", name, t, dtype, dev, shape)
+  nb, nray = (int(n) for n in chk("pnt", pnt, torch.float32, None, None, 3).shape[:2])
+  nbv = int(chk("vec", vec, torch.float32, None, nray, 3).shape[0])
+  if nb not in (1, nworld) or nbv not in (1, nworld):
+    raise ValueError(f"rays: pnt / vec batch must be 1 or nworld = {nworld}, got {nb} / {nbv}")
+  chk("bodyexclude", bodyexclude, torch.int32, nray)
+  chk("dist", dist, torch.float32, nworld, nray)
+  chk("geomid", geomid, torch.int32, nworld, nray)
+  chk("normal", normal, torch.float32, nworld, nray, 3)
   group = None
   if geomgroup is not None:
     g = [int(x) for x in geomgroup]
@@ -113,7 +88,7 @@ def rays(m: Model, d: Data, pnt: torch.Tensor, vec: torch.Tensor, geomgroup: Opt
   from .io import cdata, cmodel
 
   L = _lib.lib()
-  args = (cmodel(m), cdata(d), ctypes.byref(rm), pnt.data_ptr(), nb, vec.data_ptr(), int(vec.shape[0]), nray, group,
+  args = (cmodel(m), cdata(d), ctypes.byref(rm), pnt.data_ptr(), nb, vec.data_ptr(), nbv, nray, group,
           int(bool(flg_static)), bodyexclude.data_ptr(), dist.data_ptr(), geomid.data_ptr(), normal.data_ptr())
   if bvh is None:
     _lib.check(L.mjw_rays(*args, _stream(d)), "mjw_rays")

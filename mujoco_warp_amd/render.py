@@ -259,23 +259,17 @@ def _ctex(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CTexture:
   dev = d.qpos.device
   nmat = int(m.nmat)
   c = _lib.CTexture()
-
-  def chk(owner, name, t, dtype, tail):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape[1:]) != tail:
-      raise ValueError(f"{who}: {owner}.{name} must be a contiguous {dtype} tensor of shape (n,{' ' + str(tail) if tail else ''}) on {dev}")
-    return t
-
   for name, dtype, tail in (("tex_data", torch.int32, ()), ("tex_adr", torch.int32, ()), ("tex_width", torch.int32, ()), ("tex_height", torch.int32, ()),
                             ("mesh_texcoord", torch.float32, (2,)), ("mesh_texcoordadr", torch.int32, ()), ("mesh_facetexcoord", torch.int32, (3,))):
-    setattr(c, name, chk("rc", name, getattr(rc, name), dtype, tail).data_ptr())
+    setattr(c, name, _lib.check_tensor(who, "rc." + name, getattr(rc, name), dtype, dev, (None,) + tail).data_ptr())
   ntex = int(rc.tex_adr.shape[0])
   if int(rc.tex_width.shape[0]) != ntex or int(rc.tex_height.shape[0]) != ntex:
     raise ValueError(f"{who}: rc.tex_adr / tex_width / tex_height must hold the same number of textures")
   nmesh, nface = int(rc.mesh_texcoordadr.shape[0]), int(rc.mesh_facetexcoord.shape[0])
   if nmesh not in (0, int(m.nmesh)) or nface not in (0, int(m.nmeshface)):
     raise ValueError(f"{who}: rc.mesh_texcoordadr / mesh_facetexcoord must hold {m.nmesh} meshes and {m.nmeshface} faces (or none)")
-  texid, texrep = getattr(m, "mat_texid", None), getattr(m, "mat_texrepeat", None)
-  texid, texrep = chk("m", "mat_texid", texid, torch.int32, (nmat, 10)), chk("m", "mat_texrepeat", texrep, torch.float32, (nmat, 2))
+  texid = _lib.check_tensor(who, "m.mat_texid", getattr(m, "mat_texid", None), torch.int32, dev, (None, nmat, 10))
+  texrep = _lib.check_tensor(who, "m.mat_texrepeat", getattr(m, "mat_texrepeat", None), torch.float32, dev, (None, nmat, 2))
   if texid.shape[0] < 1 or texrep.shape[0] < 1:
     raise ValueError(f"{who}: m.mat_texid / m.mat_texrepeat need a leading batch dimension of at least 1")
   c.ntex, c.ntexdata, c.nmat, c.nmesh, c.ntexcoord, c.nmeshface = ntex, int(rc.tex_data.shape[0]), nmat, nmesh, int(rc.mesh_texcoord.shape[0]), nface
@@ -289,45 +283,46 @@ def _crender(rc: RenderContext) -> _lib.CRender:
   c = _lib.CRender()
   c.group_mask, c.use_shadows = int(rc.group_mask), int(bool(rc.use_shadows))
   c.nrender, c.ntile, c.tile_threads = int(rc.nrender), int(rc.tile.shape[0]), int(rc.tile_threads)
-  for name in ("cam_id_map", "cam_res", "rgb_adr", "depth_adr", "seg_adr", "tile", "light_type", "light_active", "light_castshadow"):
-    t = getattr(rc, name)
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != rc.rgb_data.device:
-      raise ValueError(f"render: rc.{name} must be a contiguous int32 tensor on {rc.rgb_data.device}")
-    setattr(c, name, t.data_ptr())
-  n = int(rc.nrender)
-  if rc.cam_res.numel() != 2 * n or any(getattr(rc, k).numel() != n for k in ("cam_id_map", "rgb_adr", "depth_adr", "seg_adr")) or rc.tile.dim() != 2 \
-      or rc.tile.shape[1] != 4 or len(rc._res) != n:
-    raise ValueError(f"render: the context's camera tables must hold {n} cameras and its tile table rows of 4")
-  if rc.light_type.numel() != rc._nlight or rc.light_active.numel() != rc._nlight or rc.light_castshadow.numel() != rc._nlight:
-    raise ValueError(f"render: rc.light_type / light_active / light_castshadow must hold {rc._nlight} values")
-  nworld = int(rc.nworld)
-  for name, dtype, ld in (("rgb", torch.int32, "rgb_ld"), ("depth", torch.float32, "depth_ld"), ("seg", torch.int32, "seg_ld")):
-    t = getattr(rc, name + "_data")
+  n, nl, dev = int(rc.nrender), int(rc._nlight), rc.rgb_data.device
+  if len(rc._res) != n:
+    raise ValueError(f"render: the context's host tables must hold {n} cameras")
+  for name, shape in (("cam_id_map", (n,)), ("cam_res", (n, 2)), ("rgb_adr", (n,)), ("depth_adr", (n,)), ("seg_adr", (n,)), ("tile", (None, 4)),
+                      ("light_type", (nl,)), ("light_active", (nl,)), ("light_castshadow", (nl,))):
+    setattr(c, name, _lib.check_tensor("render", "rc." + name, getattr(rc, name), torch.int32, dev, shape).data_ptr())
+  for name, dtype in (("rgb", torch.int32), ("depth", torch.float32), ("seg", torch.int32)):
+    t = _lib.check_tensor("render", f"rc.{name}_data", getattr(rc, name + "_data"), dtype, dev, (int(rc.nworld), None))
     need = max((a + w * h for a, (w, h) in zip(rc._adr[name], rc._res) if a >= 0), default=0)
-    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.dim() != 2 or t.shape[0] != nworld or t.shape[1] < need
-        or t.device != rc.rgb_data.device):
-      raise ValueError(f"render: rc.{name}_data must be a contiguous {dtype} tensor of shape ({nworld}, >= {need})")
+    if t.shape[1] < need:
+      raise ValueError(f"render: rc.{name}_data must hold {need} pixels per world, it holds {t.shape[1]}")
     setattr(c, name, t.data_ptr())
-    setattr(c, ld, int(t.shape[1]))
+    setattr(c, name + "_ld", int(t.shape[1]))
   return c
 
 
-def _cbvh(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CBvh:
-  """mjw_bvh_t of the context's trees; ValueError when the context was made for another model or nworld."""
-  nmesh, nface = int(rc._nmesh), int(rc._nmeshface)
-  if nmesh != int(m.nmesh) or nface != int(m.nmeshface):
-    raise ValueError(f"{who}: the render context was made for a model with {nmesh} meshes and {nface} mesh faces, "
-                     f"this one has {m.nmesh} and {m.nmeshface}")
+def _made_for(who: str, rc: RenderContext, m: Model, d: Data) -> None:
+  """The one check per call (render, refit_bvh, rays) that the context was made for this nworld, device and model."""
   if int(rc.nworld) != int(d.nworld):
     raise ValueError(f"{who}: the render context was made for nworld = {rc.nworld}, the Data has {d.nworld}")
+  if rc.rgb_data.device != d.qpos.device:
+    raise ValueError(f"{who}: the render context is on {rc.rgb_data.device}, the Data is on {d.qpos.device}")
+  names = ["cameras", "lights", "meshes", "mesh faces"]
+  made, have = [rc._ncam_model, rc._nlight, rc._nmesh, rc._nmeshface], [m.ncam, m.nlight, m.nmesh, m.nmeshface]
+  if _is_flex(rc):
+    names += ["flexes", "flex vertices", "flex elements", "flex edges"]
+    made, have = made + list(rc._flex_counts), have + [m.nflex, m.nflexvert, m.nflexelem, m.nflexedge]
+  if [int(x) for x in made] != [int(x) for x in have]:
+    say = lambda counts: ", ".join(f"{int(x)} {name}" for x, name in zip(counts, names))
+    raise ValueError(f"{who}: the render context was made for a model with {say(made)}; this one has {say(have)}")
+
+
+def _cbvh(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CBvh:
+  """mjw_bvh_t of the context's trees (the caller has made the `_made_for` check; the builders share one signature,
+  this one reads nothing of m)."""
+  nmesh, nface = int(rc._nmesh), int(rc._nmeshface)
   dev = d.qpos.device
-  node, tri, adr = rc.mesh_bvh_node, rc.mesh_bvh_tri, rc.mesh_bvh_adr
-  for name, t, dtype, tail in (("mesh_bvh_node", node, torch.float32, (NODE_WORDS,)), ("mesh_bvh_tri", tri, torch.int32, ()),
-                               ("mesh_bvh_adr", adr, torch.int32, (4,))):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape[1:]) != tail:
-      raise ValueError(f"{who}: rc.{name} must be a contiguous {dtype} tensor of shape (n,{' %d' % tail[0] if tail else ''}) on {dev}")
-  if int(tri.shape[0]) != nface or int(adr.shape[0]) != nmesh:
-    raise ValueError(f"{who}: rc.mesh_bvh_tri / mesh_bvh_adr must hold {nface} faces and {nmesh} meshes")
+  node = _lib.check_tensor(who, "rc.mesh_bvh_node", rc.mesh_bvh_node, torch.float32, dev, (None, NODE_WORDS))
+  tri = _lib.check_tensor(who, "rc.mesh_bvh_tri", rc.mesh_bvh_tri, torch.int32, dev, (nface,))
+  adr = _lib.check_tensor(who, "rc.mesh_bvh_adr", rc.mesh_bvh_adr, torch.int32, dev, (nmesh, 4))
   if int(rc.bvh_leaf_size) > BVH_LEAF or int(rc.bvh_max_depth) > BVH_MAX_DEPTH:
     raise ValueError(f"{who}: the context's BVH has leaves of {rc.bvh_leaf_size} triangles and {rc.bvh_max_depth} levels; "
                      f"the kernel takes {BVH_LEAF} and {BVH_MAX_DEPTH}")
@@ -350,30 +345,18 @@ def _is_flex(rc: RenderContext) -> bool:
 
 
 def _cflex(rc: RenderContext, m: Model, d: Data, who: str) -> _lib.CFlexRender:
-  """mjw_flexrender_t of a context made with render_flex; ValueError when it was made for another model or nworld,
-  or when a table has not the shape its counts ask for (the kernels trust the counts)."""
+  """mjw_flexrender_t of a context made with render_flex (the caller has made the `_made_for` check); ValueError when
+  a table has not the shape its counts ask for (the kernels trust the counts)."""
   nflex, nfv, nelem, nedge = rc._flex_counts
-  if (nflex, nfv, nelem, nedge) != (int(m.nflex), int(m.nflexvert), int(m.nflexelem), int(m.nflexedge)):
-    raise ValueError(f"{who}: the render context was made for a model with {nflex} flexes, {nfv} flex vertices, {nelem} elements and {nedge} edges, "
-                     f"this one has {m.nflex}, {m.nflexvert}, {m.nflexelem} and {m.nflexedge}")
-  if int(rc.nworld) != int(d.nworld):
-    raise ValueError(f"{who}: the render context was made for nworld = {rc.nworld}, the Data has {d.nworld}")
   dev = d.qpos.device
   c = _lib.CFlexRender()
+  nface = int(_lib.check_tensor(who, "rc.flex_corner", rc.flex_corner, torch.int32, dev, (None, 3, 3)).shape[0])
+  rows = dict(flex_info=nflex, flex_radius=nflex, flex_rgba=nflex, flex_elem_vert=nelem, flex_edge_vert=nedge, flex_inc_adr=nfv + 1, flex_bvh_tri=nface)
   for cname, name, dtype, tail in _FLEX_TABLES:
-    t = getattr(rc, name)
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape[1:]) != tail:
-      raise ValueError(f"{who}: rc.{name} must be a contiguous {dtype} tensor of shape (n, {tail}) on {dev}")
-    setattr(c, cname, t.data_ptr())
-  nface, nnode = int(rc.flex_corner.shape[0]), int(rc.flex_bvh_node.shape[0])
-  want = dict(flex_info=nflex, flex_radius=nflex, flex_rgba=nflex, flex_elem_vert=nelem, flex_edge_vert=nedge, flex_inc_adr=nfv + 1, flex_bvh_tri=nface)
-  for name, n in want.items():
-    if int(getattr(rc, name).shape[0]) != n:
-      raise ValueError(f"{who}: rc.{name} must hold {n} rows")
+    setattr(c, cname, _lib.check_tensor(who, "rc." + name, getattr(rc, name), dtype, dev, (rows.get(name),) + tail).data_ptr())
+  nnode = int(rc.flex_bvh_node.shape[0])
   for name, shape in (("flex_node_box", (int(rc.nworld), nnode + nflex, 6)), ("flexvert_norm", (int(rc.nworld), nfv, 3))):
-    t = getattr(rc, name)
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
-      raise ValueError(f"{who}: rc.{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+    _lib.check_tensor(who, "rc." + name, getattr(rc, name), torch.float32, dev, shape)
   if int(rc.flex_bvh_max_depth) > BVH_MAX_DEPTH:
     raise ValueError(f"{who}: the context's flex trees have {rc.flex_bvh_max_depth} levels; the kernel takes {BVH_MAX_DEPTH}")
   c.nflex, c.nflexvert, c.nflexelem, c.nflexedge, c.nface, c.nnode = nflex, nfv, nelem, nedge, nface, nnode
@@ -404,14 +387,7 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   normal of a flex triangle its winding normal turned to face the ray; flexes throw and receive shadows like geoms."""
   if not isinstance(rc, RenderContext):
     raise ValueError("render: rc must be a RenderContext from create_render_context")
-  dev = d.qpos.device
-  if int(rc.nworld) != int(d.nworld):
-    raise ValueError(f"render: the render context was made for nworld = {rc.nworld}, the Data has {d.nworld}")
-  if rc.rgb_data.device != dev:
-    raise ValueError(f"render: the render context is on {rc.rgb_data.device}, the Data is on {dev}")
-  if int(rc._ncam_model) != int(m.ncam) or int(rc._nlight) != int(m.nlight):
-    raise ValueError(f"render: the render context was made for a model with {rc._ncam_model} cameras and {rc._nlight} lights, "
-                     f"this one has {m.ncam} and {m.nlight}")
+  _made_for("render", rc, m, d)
   from .forward import _stream
   from .io import cdata, cmodel
   from .ray import _ray_model
@@ -419,29 +395,21 @@ def render(m: Model, d: Data, rc: RenderContext) -> None:
   bvh = _cbvh(rc, m, d, "render")
   rm = _ray_model(m)
   c = _crender(rc)
-  fr = None
-  if _is_flex(rc):
-    fr = _cflex(rc, m, d, "render")
-    if not rc._flex_refit:
-      raise ValueError("render: the context's flex trees have never been refit: call refit_bvh(m, d, rc) after the step and before render")
-  if bool(getattr(rc, "has_textures", False)):
-    tex = _ctex(rc, m, d, "render")
-    if c.ntile == 0:
-      return
-    rcode = _lib.lib().mjw_render_tex(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), ctypes.byref(fr) if fr is not None else None,
-                                      ctypes.byref(tex), _stream(d))
-    _lib.check(rcode, "mjw_render_tex")
-    return
-  if fr is not None:
-    if c.ntile == 0:
-      return
-    rcode = _lib.lib().mjw_render_flex(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), ctypes.byref(fr), _stream(d))
-    _lib.check(rcode, "mjw_render_flex")
-    return
+  fr = _cflex(rc, m, d, "render") if _is_flex(rc) else None
+  if fr is not None and not rc._flex_refit:
+    raise ValueError("render: the context's flex trees have never been refit: call refit_bvh(m, d, rc) after the step and before render")
+  tex = _ctex(rc, m, d, "render") if bool(getattr(rc, "has_textures", False)) else None
   if c.ntile == 0:
     return
-  rcode = _lib.lib().mjw_render_bvh(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), _stream(d))
-  _lib.check(rcode, "mjw_render_bvh")
+  # the entry that takes what the context has, and its arguments after the bvh (a null flex table: no flexes)
+  if tex is not None:
+    entry, more = "mjw_render_tex", (ctypes.byref(fr) if fr is not None else None, ctypes.byref(tex))
+  elif fr is not None:
+    entry, more = "mjw_render_flex", (ctypes.byref(fr),)
+  else:
+    entry, more = "mjw_render_bvh", ()
+  rcode = getattr(_lib.lib(), entry)(cmodel(m), cdata(d), ctypes.byref(rm), ctypes.byref(c), ctypes.byref(bvh), *more, _stream(d))
+  _lib.check(rcode, entry)
 
 
 def refit_bvh(m: Model, d: Data, rc: RenderContext) -> None:
@@ -457,6 +425,7 @@ def refit_bvh(m: Model, d: Data, rc: RenderContext) -> None:
   from .forward import _stream
   from .io import cdata, cmodel
 
+  _made_for("refit_bvh", rc, m, d)
   fr = _cflex(rc, m, d, "refit_bvh")
   rcode = _lib.lib().mjw_flex_refit(cmodel(m), cdata(d), ctypes.byref(fr), _stream(d))
   _lib.check(rcode, "mjw_flex_refit")
