@@ -25,6 +25,7 @@
  *   mjw_render_tex        <- render.render of a context that has textures (use_textures; planes and meshes with texcoords)
  *   mjw_inverse           <- inverse.inverse's constraint + combine  inverse.py, solver.py init_context(grad=False)
  *   mjw_island            <- island.island (connected components by union-find, no tree x tree matrix) island.py:246-265
+ *   mjw_fd_perturb / mjw_fd_difference <- no reference counterpart: MuJoCo's mjd_transitionFD around mjw_step (derivative_fd.py)
  *
  * Ownership: the caller owns every buffer (device pointers below); the library
  * never allocates or frees device memory and keeps no global mutable state.
@@ -571,6 +572,77 @@ int mjw_sizeof_texture(void);
  * with a non-zero count gives -1, a negative count, a batch size under 1 or counts that differ from the model's -4. */
 int mjw_render_tex(const mjw_model_t* m, const mjw_data_t* d, const mjw_ray_model_t* rm, const mjw_render_t* rc, const mjw_bvh_t* bvh,
                    const mjw_flexrender_t* fr, const mjw_texture_t* tex, void* stream);
+
+/* Finite-difference linearisation of the step (MuJoCo's mjd_transitionFD): x' ~ A dx + B du, sensordata ~ C dx + D du,
+ * in the tangent space dx = [dq (nv), dv (nv), dact (na)], ndx = 2 nv + na, with K = ndx + nu input columns (the state
+ * columns, then ctrl).  Every perturbed copy of a world is one more world of a scratch Data: slot c of world w is
+ * scratch world c * nworld + w, slot 0 holds the nominal state, slots 1 .. ncp the + nudges of the pass's columns
+ * col0 .. col0 + ncols - 1, and with `centered` slots 1 + ncp .. 2 ncp their - nudges, where ncp is the columns a pass
+ * holds: ncol_pass = 1 + 2 ncp centred, 1 + ncp forward.  mjw_fd_perturb fills the slots, the caller steps the
+ * scratch Data, mjw_fd_difference turns the stepped slots into the pass's columns of A..D.  The struct holds the
+ * pointers of the nominal Data's (n_*) and the scratch Data's (s_*) fields so that the kernels do not take two
+ * mjw_data_t by value; every pointer is a device pointer, an array of zero size may be null.
+ *
+ * The ctrl columns follow MuJoCo's range rule for an actuator with actuator_ctrllimited while CLAMPCTRL is not
+ * disabled: the + nudge is made only if ctrl and ctrl + eps lie inside ctrlrange, the - nudge only if `centered` or the
+ * + nudge was impossible, and ctrl - eps and ctrl lie inside; the column is then centred, forward, backward or zero,
+ * per world.  A forward context keeps the - nudge of such a column in the column's one slot.  A slot whose nudge is
+ * not made, and every slot past the pass's ncols columns, holds the nominal state. */
+typedef struct mjw_fd_t {
+  int32_t nworld;     /* worlds of the nominal Data; the scratch Data holds ncol_pass * nworld */
+  int32_t ncol;       /* K = 2 nv + na + nu, checked against the model */
+  int32_t ncol_pass;  /* slots per world */
+  int32_t centered;   /* 0 / 1 */
+  int32_t col0;       /* first column of this pass */
+  int32_t ncols;      /* columns of this pass, 1 .. ncp */
+  const float* n_time;            /* (nworld,) */
+  const float* n_qpos;            /* (nworld, nq) */
+  const float* n_qvel;            /* (nworld, nv) */
+  const float* n_act;             /* (nworld, na) */
+  const float* n_ctrl;            /* (nworld, nu) */
+  const float* n_qacc_warmstart;  /* (nworld, nv) */
+  const float* n_qfrc_applied;    /* (nworld, nv) */
+  const float* n_xfrc_applied;    /* (nworld, nbody, 6) */
+  const float* n_mocap_pos;       /* (nworld, nmocap, 3) */
+  const float* n_mocap_quat;      /* (nworld, nmocap, 4) */
+  const int32_t* n_eq_active;     /* (nworld, neq) */
+  float* s_time;                  /* the same fields of the scratch Data, (ncol_pass * nworld, ...) */
+  float* s_qpos;
+  float* s_qvel;
+  float* s_act;
+  float* s_ctrl;
+  float* s_qacc_warmstart;
+  float* s_qfrc_applied;
+  float* s_xfrc_applied;
+  float* s_mocap_pos;
+  float* s_mocap_quat;
+  int32_t* s_eq_active;
+  const float* s_sensordata;      /* (ncol_pass * nworld, nsensordata); read by mjw_fd_difference when C is given */
+  float* A;                       /* (nworld, ndx, lda) */
+  float* B;                       /* (nworld, ndx, ldb); unused when nu == 0 */
+  float* C;                       /* (nworld, nsensordata, ldc) or null (then D is null too) */
+  float* D;                       /* (nworld, nsensordata, ldd); unused when nu == 0 */
+  int64_t lda, ldb, ldc, ldd;     /* floats between consecutive rows: >= ndx, nu, ndx, nu */
+} mjw_fd_t;
+int mjw_sizeof_fd(void);
+/* Fills every slot of the scratch Data: one wave per scratch world copies, bitwise, the world's time, qpos, qvel,
+ * act, ctrl, qacc_warmstart, qfrc_applied, xfrc_applied, eq_active, mocap_pos and mocap_quat; then one lane applies
+ * the slot's nudge.  Column k < nv nudges the position in the tangent space (slide, hinge, free translation: add
+ * +-eps; free rotation and ball: quat <- normalize(quat * exp(+-eps e)), the rotation vector in the local frame, as
+ * mj_integratePos), the next nv columns add to qvel, the next na to act, the last nu to ctrl under the range rule.
+ * `d` is the nominal Data and is only read; A..D are not used.  Allocates nothing, no atomics (graph capturable).
+ * nworld <= 0 is a successful no-op; null arguments or arrays give -1; nv == 0, eps <= 0, sizes that differ from the
+ * model's or the Data's, or a column range outside 0 .. K give -4. */
+int mjw_fd_perturb(const mjw_model_t* m, const mjw_data_t* d, const mjw_fd_t* fd, float eps, void* stream);
+/* Writes the pass's columns of A, B (and C, D when given) from the stepped slots: one workgroup per (world, tile of
+ * columns) stages the differences of the slots' qpos, qvel, act and sensordata in LDS (rows padded to an odd stride)
+ * and stores them with lanes along the last dimension.  With h = 2 eps for a centred column (y- to y+) and eps for a
+ * one-sided one (nominal to +, or - to nominal), position rows are mj_differentiatePos (scalar joints and free
+ * translation (q2 - q1) / h; quaternions log(conj(q1) * q2) / h, the angle in (-pi, pi], once per column and joint),
+ * every other row (y2 - y1) / h, a true division; a column without a nudge is zero.  Writes rows 0 .. ndx - 1
+ * (nsensordata - 1) of columns col0 .. col0 + ncols - 1 and nothing else.  Errors as mjw_fd_perturb; more rows than
+ * one column's staging holds (2 nv + na + nsensordata > 12287) give -2. */
+int mjw_fd_difference(const mjw_model_t* m, const mjw_data_t* d, const mjw_fd_t* fd, float eps, void* stream);
 
 #ifdef __cplusplus
 }

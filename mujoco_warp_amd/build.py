@@ -6,7 +6,7 @@ import sys
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
-SOURCES = [os.path.join(_PKG, "csrc", n) for n in ("mjw_step.hip", "mjw_dense.hip", "mjw_sensor.hip", "mjw_rk4.hip", "mjw_sparse.hip", "mjw_kat.hip", "mjw_ray.hip", "mjw_render.hip", "mjw_inverse.hip", "mjw_island.hip", "mjw_flexrender.hip")]
+SOURCES = [os.path.join(_PKG, "csrc", n) for n in ("mjw_step.hip", "mjw_dense.hip", "mjw_sensor.hip", "mjw_rk4.hip", "mjw_sparse.hip", "mjw_kat.hip", "mjw_ray.hip", "mjw_render.hip", "mjw_inverse.hip", "mjw_island.hip", "mjw_flexrender.hip", "mjw_fd.hip")]
 # every header next to the sources (a hand-kept list once missed mjw_trn.h, so sources_hash() and
 # needs_build() did not see edits to the transmission code)
 HEADERS = sorted(os.path.join(_PKG, "csrc", n) for n in os.listdir(os.path.join(_PKG, "csrc")) if n.endswith(".h"))
