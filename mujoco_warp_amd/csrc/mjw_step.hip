@@ -847,7 +847,30 @@ __device__ __forceinline__ int tendon_rows(const mjw_model_t& m, const mjw_data_
   return added;
 }
 
-template <bool BOX, bool TEN, bool POOL = false>
+// the relative Jacobian (body 2 minus body 1) of dof i at the staged contact `rec`; zero for i >= nv
+__device__ __forceinline__ void contact_jac(const Lay& L, const float* s, const float* rec, int i, int nv, int db, int dend, float* jdp,
+                                            float* jdr) {
+  for (int k = 0; k < 3; k++) jdp[k] = jdr[k] = 0.0f;
+  if (i < nv) {
+    const int* reci = reinterpret_cast<const int*>(rec);
+    float j1p[3], j1r[3], j2p[3], j2r[3];
+    jac_dof_root(L, s, rec + 2, reci[21] & 0xffff, reci[32] & 0xffff, i, db, dend, j1p, j1r);
+    jac_dof_root(L, s, rec + 2, reci[21] >> 16, reci[32] >> 16, i, db, dend, j2p, j2r);
+    for (int k = 0; k < 3; k++) { jdp[k] = j2p[k] - j1p[k]; jdr[k] = j2r[k] - j1r[k]; }
+  }
+}
+
+// contact direction k applied to the relative Jacobian: frame row k on the translational part (k < 3), frame row
+// k - 3 on the rotational part.  An elliptic row is its direction; a pyramid edge is normal +- friction * direction.
+__device__ __forceinline__ float contact_Jdir(const float* frame, const float* jdp, const float* jdr, int k) {
+  if (k < 3) return frame[3 * k] * jdp[0] + frame[3 * k + 1] * jdp[1] + frame[3 * k + 2] * jdp[2];
+  return frame[3 * (k - 3)] * jdr[0] + frame[3 * (k - 3) + 1] * jdr[1] + frame[3 * (k - 3) + 2] * jdr[2];
+}
+
+// PAIR: the launch guarantees nv <= 32 (the fused step: 17..28; every direct-mode launch: dense_ok), so without
+// body transmissions the contact rows are built two contacts per pass and the one-contact loop is not compiled;
+// otherwise that is chosen at run time
+template <bool BOX, bool TEN, bool POOL = false, bool PAIR = false>
 __device__ __forceinline__ void collision_and_constraints(const mjw_model_t& m, const mjw_data_t& d, const Lay& L, WS& w) {
   const int wid = w.wid, lane = w.lane;
   float* s = w.s;
@@ -859,9 +882,13 @@ __device__ __forceinline__ void collision_and_constraints(const mjw_model_t& m, 
   const int np = m.nv_pad;
   const int kJ = L.J >= 0 ? nv : np;  // global rows also get their zero padding
   const int CM = L.cmax;
-  // this lane's dof body and its DFS subtree end (jac_dof's ancestor test), loaded once
-  const int dof_db = lane < nv ? m.dof_bodyid[lane] : 0;
-  const int dof_dend = lane < nv ? m.body_subtree_end[dof_db] : 0;
+  // contact rows two contacts per pass (below): body transmissions take the whole wave per contact
+  const bool pair = (PAIR || nv <= 32) && !(TEN && m.nbodytrn);
+  // this lane's dof body and its DFS subtree end (jac_dof's ancestor test), loaded once; paired, lanes 32-63
+  // hold dofs 0-31 again (every other user tests lane < nv)
+  const int ldof = pair ? (lane & 31) : lane;
+  const int dof_db = ldof < nv ? m.dof_bodyid[ldof] : 0;
+  const int dof_dend = ldof < nv ? m.body_subtree_end[dof_db] : 0;
   WSYNC();  // contact staging may alias the qM region read by crb_qM
   PROF_T0_SUB();
 
@@ -1363,54 +1390,106 @@ __device__ __forceinline__ void collision_and_constraints(const mjw_model_t& m, 
         }
       }
       PROF_MARK_SUB(PH_C_POOL);
-      // J entries: lane = dof, loop over staged contacts; efc_vel = J qvel by wave reduction
-      for (int cc = 0; cc < nstage; cc++) {
-        const float* rec = s + L.con + cc * CREC;
-        const int* reci = reinterpret_cast<const int*>(rec);
-        int condim = reci[28] & 0xff;
-        int r0 = si[L.iscratch + cc];
-        float pos = rec[0] - rec[1];
-        if (TEN && m.nbodytrn && (POOL || gbase + cc < d.naconmax) && reci[29] >= 0 && reci[30] >= 0)  // smooth.py:2448-2602
-          body_trn_contact(m, s + L.subtree_com, s + L.cdof, rec + 2, rec + 5, reci[22] & 0xffff, reci[22] >> 16, s + L.act_mom, si + L.act_nnz,
-                           L.amax, lane);
-        if (!(pos < 0.0f) || (!POOL && gbase + cc >= d.naconmax)) continue;
-        int nr = condim == 1 ? 1 : (ell ? condim : 2 * (condim - 1));
-        const int b1 = reci[21] & 0xffff, b2 = reci[21] >> 16;
-        const float* cpos = rec + 2;
-        const float* frame = rec + 5;
-        const int i = lane;
-        float jdp[3] = {0.0f, 0.0f, 0.0f}, jdr[3] = {0.0f, 0.0f, 0.0f};
-        if (i < nv) {
-          float j1p[3], j1r[3], j2p[3], j2r[3];
-          jac_dof_root(L, s, cpos, b1, reci[32] & 0xffff, i, dof_db, dof_dend, j1p, j1r);
-          jac_dof_root(L, s, cpos, b2, reci[32] >> 16, i, dof_db, dof_dend, j2p, j2r);
-          for (int k = 0; k < 3; k++) { jdp[k] = j2p[k] - j1p[k]; jdr[k] = j2r[k] - j1r[k]; }
-        }
+      // J entries; efc_vel = J qvel by wave reduction
+      if (pair) {
+        // nv <= 32: two staged contacts per pass, lane 32h + i = contact 2p + h, dof i.  Everything a contact
+        // owns (record, first row, row count, the pool test) is per half; `break` / `continue` of the loop below
+        // become the row count nr = 0 (dropped, not penetrating, the missing partner of an odd last contact) or
+        // its cut at njmax.  Each row's J.qvel is one half of dsum_halves and is the number dsum gives below:
+        // there lanes >= 32 add zeros, so rows 2 and 3 stay 0 and dsum's last step (row_bcast:31) is the exact
+        // 0 + (R1 + R0); half 1 runs the same quad_perm, row_ror and row_bcast:15 steps on the same
+        // lane-relative values.  Only an all-zero sum could differ, by its sign: with every lane -0 (possible at
+        // nv = 32 alone: below that a lane past nv adds +0) the half sum is -0 where dsum's 0 + (-0) is +0, so
+        // the stored value is `+ 0.0f`, which changes no other number.  Up to four rows of a pass form their
+        // Jval and store it first; the four reductions then run back to back (independent DPP chains).
+        const int half = lane >> 5, i = lane & 31;
         const float qv = i < nv ? qvel[i] : 0.0f;
-        float Jn = frame[0] * jdp[0] + frame[1] * jdp[1] + frame[2] * jdp[2];
-        for (int dimid = 0; dimid < nr; dimid++) {
-          int r = r0 + dimid;
-          if (r >= njmax) break;
-          float Jval = Jn;
-          if (ell && condim > 1) {
-            // elliptic (constraint.py:2151-2160): row dimid is frame row dimid applied to the relative
-            // translational (dimid < 3) or rotational jacobian
-            if (dimid > 0) {
-              const float* fr = dimid < 3 ? frame + 3 * dimid : frame + 3 * (dimid - 3);
-              const float* jd = dimid < 3 ? jdp : jdr;
-              Jval = fr[0] * jd[0] + fr[1] * jd[1] + fr[2] * jd[2];
+        for (int c0 = 0; c0 < nstage; c0 += 2) {
+          const int cc = c0 + half;
+          const bool have = cc < nstage;
+          const float* rec = s + L.con + (have ? cc : c0) * CREC;
+          const int* reci = reinterpret_cast<const int*>(rec);
+          const int condim = reci[28] & 0xff;
+          const int r0 = si[L.iscratch + (have ? cc : c0)];
+          const float pos = rec[0] - rec[1];
+          int nr = condim == 1 ? 1 : (ell ? condim : 2 * (condim - 1));
+          if (!have || !(pos < 0.0f) || (!POOL && gbase + cc >= d.naconmax)) nr = 0;
+          nr = min(nr, njmax - r0);
+          const int nrmax = max(__builtin_amdgcn_readlane(nr, 0), __builtin_amdgcn_readlane(nr, 32));
+          if (nrmax <= 0) continue;
+          const float* frame = rec + 5;
+          float jdp[3], jdr[3];
+          contact_jac(L, s, rec, i, nv, dof_db, dof_dend, jdp, jdr);
+          const float Jn = frame[0] * jdp[0] + frame[1] * jdp[1] + frame[2] * jdp[2];
+          for (int d0 = 0; d0 < nrmax; d0 += 4) {
+            float jq[4];
+#pragma unroll
+            for (int k = 0; k < 4; k += 2) {
+              const int dimid = d0 + k;  // even: rows dimid, dimid + 1 are the two signs of one pyramid edge
+              float Ja = Jn, Jb = Jn;
+              if (ell && condim > 1) {  // elliptic (constraint.py:2151-2160): row dimid is direction dimid
+                if (dimid > 0) Ja = contact_Jdir(frame, jdp, jdr, dimid);
+                Jb = contact_Jdir(frame, jdp, jdr, dimid + 1);
+              } else if (condim > 1) {
+                const int dimid2 = dimid / 2 + 1;
+                const float frii = rec[14 + dimid2 - 1];
+                const float Ji = contact_Jdir(frame, jdp, jdr, dimid2);
+                Ja = Jn + Ji * frii;
+                Jb = Jn - Ji * frii;
+              }
+              const bool ra = dimid < nr, rb = dimid + 1 < nr;
+              if (ra && i < kJ) put_J(d, L, s, wid, np, r0 + dimid, i, i < nv ? Ja : 0.0f);
+              if (rb && i < kJ) put_J(d, L, s, wid, np, r0 + dimid + 1, i, i < nv ? Jb : 0.0f);
+              jq[k] = (ra && i < nv) ? Ja * qv : 0.0f;
+              jq[k + 1] = (rb && i < nv) ? Jb * qv : 0.0f;
             }
-          } else if (condim > 1) {
-            int dimid2 = dimid / 2 + 1;
-            float frii = rec[14 + dimid2 - 1];
-            float Ji;
-            if (dimid2 < 3) Ji = frame[3 * dimid2] * jdp[0] + frame[3 * dimid2 + 1] * jdp[1] + frame[3 * dimid2 + 2] * jdp[2];
-            else Ji = frame[3 * (dimid2 - 3)] * jdr[0] + frame[3 * (dimid2 - 3) + 1] * jdr[1] + frame[3 * (dimid2 - 3) + 2] * jdr[2];
-            Jval = (dimid % 2 == 0) ? Jval + Ji * frii : Jval - Ji * frii;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              float lo, hi;
+              dsum_halves(jq[k], lo, hi);
+              jq[k] = (half ? hi : lo) + 0.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+              if (i == 0 && d0 + k < nr) s[L.jqvel + r0 + d0 + k] = jq[k];
           }
-          if (i < kJ) put_J(d, L, s, wid, np, r, i, i < nv ? Jval : 0.0f);
-          float jq = dsum(i < nv ? Jval * qv : 0.0f);
-          if (lane == 0) s[L.jqvel + r] = jq;
+        }
+      } else {
+        // nv > 32, or body transmissions (body_trn_contact takes the whole wave per contact): lane = dof, one
+        // staged contact at a time
+        for (int cc = 0; cc < nstage; cc++) {
+          const float* rec = s + L.con + cc * CREC;
+          const int* reci = reinterpret_cast<const int*>(rec);
+          int condim = reci[28] & 0xff;
+          int r0 = si[L.iscratch + cc];
+          float pos = rec[0] - rec[1];
+          if (TEN && m.nbodytrn && (POOL || gbase + cc < d.naconmax) && reci[29] >= 0 && reci[30] >= 0)  // smooth.py:2448-2602
+            body_trn_contact(m, s + L.subtree_com, s + L.cdof, rec + 2, rec + 5, reci[22] & 0xffff, reci[22] >> 16, s + L.act_mom,
+                             si + L.act_nnz, L.amax, lane);
+          if (!(pos < 0.0f) || (!POOL && gbase + cc >= d.naconmax)) continue;
+          int nr = condim == 1 ? 1 : (ell ? condim : 2 * (condim - 1));
+          const float* frame = rec + 5;
+          const int i = lane;
+          float jdp[3], jdr[3];
+          contact_jac(L, s, rec, i, nv, dof_db, dof_dend, jdp, jdr);
+          const float qv = i < nv ? qvel[i] : 0.0f;
+          float Jn = frame[0] * jdp[0] + frame[1] * jdp[1] + frame[2] * jdp[2];
+          for (int dimid = 0; dimid < nr; dimid++) {
+            int r = r0 + dimid;
+            if (r >= njmax) break;
+            float Jval = Jn;
+            if (ell && condim > 1) {  // elliptic (constraint.py:2151-2160): row dimid is direction dimid
+              if (dimid > 0) Jval = contact_Jdir(frame, jdp, jdr, dimid);
+            } else if (condim > 1) {
+              const int dimid2 = dimid / 2 + 1;
+              const float frii = rec[14 + dimid2 - 1];
+              const float Ji = contact_Jdir(frame, jdp, jdr, dimid2);
+              Jval = (dimid % 2 == 0) ? Jval + Ji * frii : Jval - Ji * frii;
+            }
+            if (i < kJ) put_J(d, L, s, wid, np, r, i, i < nv ? Jval : 0.0f);
+            float jq = dsum(i < nv ? Jval * qv : 0.0f);
+            if (lane == 0) s[L.jqvel + r] = jq;
+          }
         }
       }
       WSYNC();
@@ -2702,7 +2781,7 @@ struct FwdArgs {
 };
 #define FA (fresh_args<FwdArgs>())
 
-template <int STAGES, bool BOX, bool TEN>
+template <int STAGES, bool BOX, bool TEN, bool PAIR = false>
 __device__ __forceinline__ void run_stages(const mjw_model_t& m, const mjw_data_t& d, const Lay& L, WS& w) {
   PROF_T0();
   load_state(FA.m, FA.d, FA.L, w);
@@ -2727,7 +2806,7 @@ __device__ __forceinline__ void run_stages(const mjw_model_t& m, const mjw_data_
       body_trn_init(m, w.s + L.act_mom, w.si + L.act_nnz, L.amax, w.lane);
       WSYNC();
     }
-    collision_and_constraints<BOX, TEN, (STAGES & ST_POOL) != 0>(FA.m, FA.d, FA.L, w);
+    collision_and_constraints<BOX, TEN, (STAGES & ST_POOL) != 0, PAIR>(FA.m, FA.d, FA.L, w);
     PROF_MARK(PH_COLL);
     transmission<TEN>(FA.m, FA.d, FA.L, w);
     PROF_MARK(PH_TRN);
@@ -2764,7 +2843,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(fwd_wav
   w.lane = lane_id();
   if (w.wid >= d.nworld) return;
   WLOG_T0();
-  run_stages<STAGES, BOX, TEN>(m, d, L, w);
+  run_stages<STAGES, BOX, TEN, (STAGES & ST_NOFACTOR) != 0>(m, d, L, w);  // direct mode is launched for nv <= 32 only (run: dense_ok)
   WLOG_END(w.wid, 0);
 }
 
@@ -2785,7 +2864,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) st
   // the longest-first order of the previous step's solve (a permutation) when the step built it
   w.wid = d.sched ? d.world_order[b] : b;
   w.lane = lane_id();
-  run_stages<STAGES, BOX, false>(m, d, L, w);
+  run_stages<STAGES, BOX, false, true>(m, d, L, w);  // launched for nv 17..28 only (step_fused)
   __syncthreads();  // the forward outputs (global) and the LDS are the dense half's from here
   dense_world<FLAGS, NEWTON, false, NB>(m, d, w.wid, smem);
 }
@@ -3404,6 +3483,8 @@ int launch_generic(const mjw_model_t* m, const mjw_data_t* d, hipStream_t s, con
   constexpr bool nofactor = (STAGES & mjw::ST_NOFACTOR) != 0;
   if (count < 0) count = d->nworld - w0;
   if (count <= 0) return 0;
+  // the direct-mode kernels build their contact rows two per pass (PAIR: lanes 32-63 hold dofs 0-31 again)
+  if (nofactor && m->nv > 32) { g_err = std::string(name) + ": direct mode (ST_NOFACTOR) needs nv <= 32"; return -4; }
   mjw::Lay L = mjw::make_layout(*m, d->njmax, nofactor);
   size_t lds = (size_t)L.total * 4;
   static const size_t lds_pad = [] {  // occupancy experiments only (MJW_LDS_PAD bytes)
